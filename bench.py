@@ -7,12 +7,19 @@ GPU) interleaved with the policy forward, then GAE + dataset preparation and
 reference's "fps total" (rl_games a2c_common.py:46-60).  Workload: the north
 star's USV_Virtual_CaptureXY at 2^20 envs over 8 GPUs (BASELINE.json configs[4]),
 i.e. 131072 envs per GPU, PPO-MLP fp32; with --gpus N each rank owns 131072 envs
-(weak scaling) and gradients are all-reduced over RCCL every minibatch.  The
-4096-env BASELINE configs[1] line is reported as a secondary field (extra.c2), and on one GPU
-configs[2] (65536 envs, bf16 GEMMs: extra.c3) and configs[3]'s per-GPU share of each task (extra.c4_pose,
-extra.c4_track) too.
+(weak scaling) and gradients are all-reduced over RCCL every minibatch.
 
-    python bench.py [--gpus N --steps K --warmup W --envs 131072]
+A plain run does what the headline needs and no more: it builds one seed's env and agent, runs W warmup
+and K timed epochs, writes the last timed epoch's outputs if --dump-outputs is given and prints the result
+line (value, ms_per_step, the in-epoch phase split and, on several ranks, the per-rank records).
+
+--full adds every other measurement of the benchmark to that line: the seed protocol (value = the median
+over seeds 0-4), per-launch kernel timings and the two roofline objects, the fps definitions, the learning
+milestones and the sustained rate, the 4096-env BASELINE configs[1] line (extra.c2), on one GPU configs[2]
+(65536 envs, bf16 GEMMs: extra.c3) and configs[3]'s per-GPU share of each task (extra.c4_pose,
+extra.c4_track), and the CPU baseline.
+
+    python bench.py [--gpus N --steps K --warmup W --envs 131072] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -295,17 +302,83 @@ def time_epochs(agent, steps, world, local):
     return float(t.item())
 
 
-def main():
+DUMP_BUDGET_BYTES = 64 * 2 ** 20   # --dump-outputs: all files together
+DUMP_ENV_ROWS = 131072             # per-env arrays (observations, dones, env state): rows kept
+DUMP_EXP_ROWS = 65536              # per-row arrays of the experience batch (num_envs x horizon rows): rows kept
+
+
+def _dump_rows(n, keep):
+    """The rows of an n-row output that --dump-outputs keeps: all of them up to `keep`, else a fixed seeded sample
+    (sorted, without replacement), the same for every run and build."""
+    import numpy as np
+    if n <= keep:
+        return None
+    return np.sort(np.random.default_rng(20240131).choice(n, keep, replace=False))
+
+
+def dump_outputs(agent, task, out_dir, rank=0):
+    """What a caller of the timed path (A2CAgent.train_epoch) holds after its last timed epoch, as
+    out_dir/<name>.npy (float32, the fp64 running statistics as float64; flags and counters as float32):
+    the updated policy (params, Adam moments, optimiser scalars, observation / value statistics), the epoch's
+    loss and KL logs and episode meter, the env's current observations, dones and physical state, and the
+    epoch's experience batch (observations, actions, neglogp, values, returns, advantages, rewards, mu, sigma,
+    dones).  Arrays over more than DUMP_ENV_ROWS envs or DUMP_EXP_ROWS batch rows are written as a fixed seeded
+    row sample (the row numbers in env_rows.npy / exp_rows.npy).  Ranks above 0 write <name>.rank<r>.npy."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    obs = agent.obs["obs"]
+    obs = obs["state"] if isinstance(obs, dict) else obs
+    whole = {"params": agent.model_params, "adam_m": agent.adam_m, "adam_v": agent.adam_v, "opt": agent.opt[:8],
+             "obs_rms": agent.obs_rms, "val_rms": agent.val_rms, "loss_log": agent.loss_log, "kls": agent.kls,
+             "meter": agent.meter}
+    per_env = {"obs": obs, "dones": agent.dones}
+    state = getattr(task, "state", None)
+    if state is not None:
+        per_env["env_state"] = state.t()           # [8][num_envs] slab -> one row per env
+    per_row = {k: getattr(agent, k) for k in ("exp_obs", "exp_act", "exp_nlp", "exp_val", "exp_ret", "exp_adv",
+                                              "exp_rew", "exp_mu", "exp_sigma", "exp_done")}
+    arrays = {}
+    for group, keep, tag in ((whole, None, None), (per_env, DUMP_ENV_ROWS, "env_rows"),
+                             (per_row, DUMP_EXP_ROWS, "exp_rows")):
+        rows = None
+        if keep is not None:
+            rows = _dump_rows(next(iter(group.values())).shape[0], keep)
+            if rows is not None:
+                arrays[tag] = rows.astype(np.float64)
+                rows = torch.as_tensor(rows, device=agent.model_params.device)
+        for name, t in group.items():
+            t = t if rows is None else t[rows]
+            a = t.detach().cpu().numpy()
+            arrays[name] = np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float32))
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET_BYTES}-byte budget"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--envs", type=int, default=HEADLINE_ENVS,
                     help="envs per GPU (default: BASELINE configs[4]'s per-GPU share, 131072 = 2^20 / 8)")
-    ap.add_argument("--seeds", default="0,1,2,3,4",
-                    help="BASELINE.md's protocol: the headline (W warmup + K timed epochs) once per seed; `value` is "
-                         "the median, extra.seeds the per-seed values and min / max.  The first seed's run also "
-                         "carries the kernel timings, fps definitions, milestones and the sustained rate")
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement beyond the headline: the seed protocol, kernel timings and rooflines, fps "
+                         "definitions, learning milestones and the sustained rate, the secondary BASELINE configs, "
+                         "the CPU baseline (the options below that size them act under --full only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed epochs of the first seed's run, write what the last one computed as "
+                         "DIR/<name>.npy (dump_outputs: float32 / float64, at most 64 MB; same arguments, same "
+                         "inputs)")
+    ap.add_argument("--seeds", default=None,
+                    help="the headline (W warmup + K timed epochs) once per seed; `value` is the median, "
+                         "extra.seeds the per-seed values and min / max.  Default: seed 0 alone; with --full "
+                         "BASELINE.md's protocol, 0,1,2,3,4, where the first seed's run also carries the kernel "
+                         "timings, fps definitions, milestones and the sustained rate")
     ap.add_argument("--seed", type=int, default=None, help="one seed only (same as --seeds <seed>)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="eager launches (no HIP graph capture)")
@@ -322,8 +395,13 @@ def main():
     ap.add_argument("--milestone-seconds", type=float, default=25.0,
                     help="one GPU: keep training after the measurements for this many seconds: wall-clock to the "
                          "learning milestones, and `sustained` = the mean rate over these epochs (0 = skip)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    full = args.full
+    if args.seeds is None:
+        args.seeds = "0,1,2,3,4" if full else "0"
     seeds = [args.seed] if args.seed is not None else [int(x) for x in args.seeds.split(",") if x.strip()]
+    if not full:
+        seeds = seeds[:1]           # the seed protocol is a --full measurement
     args.seed = seeds[0]
     import torch
     import torch.distributed as dist
@@ -344,7 +422,7 @@ def main():
 
     # USV_BENCH_FLUSH=<MB>: write that many MB ahead of each timed env step (cache-state experiment)
     flush_mb = int(os.getenv("USV_BENCH_FLUSH", "0"))
-    flush_buf = torch.empty(flush_mb * 262144, device=f"cuda:{local}") if flush_mb else None
+    flush_buf = torch.empty(flush_mb * 262144, device=f"cuda:{local}") if flush_mb and full else None
 
     def timed_call(name, *a):
         if timing[0] and name in ("usv_env_step", "usv_env_step_part"):
@@ -358,7 +436,8 @@ def main():
             orig_call(name, *a)
 
     timing = [False]
-    _capi.call = timed_call
+    if full:
+        _capi.call = timed_call
 
     # training from the random init starts here: the wall clock to reward=30 counts from the first
     # reset (env / agent construction excluded), through warmup and timed epochs alike
@@ -369,7 +448,7 @@ def main():
 
     def note_reward():
         gr = agent.game_rewards
-        if gr.current_size == 0:
+        if not full or gr.current_size == 0:
             return
         r = float(gr.get_mean())
         now = time.perf_counter() - t_train
@@ -410,6 +489,8 @@ def main():
     note_reward()
     timed_events, agent.phase_events = agent.phase_events, None
     epoch_timed_last = agent.epoch_num
+    # what the last timed epoch left, before any later measurement trains on
+    dumped = dump_outputs(agent, task, args.dump_outputs, rank) if args.dump_outputs else None
     frames = world * args.envs * agent.horizon_length * args.steps
     value = frames / elapsed
     print(f"[bench] rank {rank}: {args.steps} epochs in {elapsed:.3f} s -> {value / 1e6:.2f} M env-steps/s",
@@ -424,6 +505,37 @@ def main():
     records = rank_records(rank_record(rank, f"cuda:{local}", task_name, agent.dp_status, elapsed_local, args.steps,
                                        phase), world)
     exchange, dp_extra = dp_fields(records)
+    # the headline: everything a plain run reports; --full adds to it below
+    out = None
+    if rank == 0:
+        out = {
+            "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None,
+            "dtype": "fp32 physics, bf16 GEMM operands / fp32 accumulate" if args.mixed_precision else "fp32",
+            "data": "synthetic (random-init policy, "
+            "randomised spawns/obstacles/DR from the reset path)",
+            "config": {"workload": (f"USV_Virtual_CaptureXY num_envs={args.envs}/GPU PPO-MLP fp32"
+                                    + (" (BASELINE configs[4] per GPU: 2^20 envs over 8 GPUs)"
+                                       if args.envs == HEADLINE_ENVS else "")
+                                    if args.task == "CaptureXY" else
+                                    f"USV_Virtual_{args.task} num_envs={args.envs}/GPU PPO-MLP fp32")
+                       + (" [mixed_precision: bf16 GEMMs]" if args.mixed_precision else ""),
+                       "num_envs_per_gpu": args.envs, "horizon_length": agent.horizon_length,
+                       "minibatch_size": agent.minibatch_size, "mini_epochs": agent.mini_epochs_num,
+                       "parallelism": f"dp{world}", "exchange": exchange, "seed": args.seed, "full": full},
+            "extra": dict(phase, **(dp_extra if world > 1 else {})),
+        }
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "after_epoch": epoch_timed_last, "arrays": dumped}
+    if not full:
+        if rank == 0:
+            out["extra"]["bench_wall_s"] = time.perf_counter() - t_start
+            print(json.dumps(out, default=float))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return out
     # the same two graphs replayed behind a spin kernel after the timed epochs: device time only (no host
     # submission inside the pairs), at a later training state (more resets per step as the policy learns)
     if agent._graph_play is not None and agent._graph_update is not None:
@@ -508,24 +620,8 @@ def main():
     ppo_ms = ppo_timer.mean_ms()
     achieved = step_bytes * args.envs / (env_ms * 1e-3) / 1e9
     ppo_tfs = PPO_FLOPS_PER_ROW * agent.minibatch_size / (ppo_ms * 1e-3) / 1e12
-    out = None
     if rank == 0:
-        out = {
-            "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None,
-            "dtype": "fp32 physics, bf16 GEMM operands / fp32 accumulate" if args.mixed_precision else "fp32",
-            "data": "synthetic (random-init policy, "
-            "randomised spawns/obstacles/DR from the reset path)",
-            "config": {"workload": (f"USV_Virtual_CaptureXY num_envs={args.envs}/GPU PPO-MLP fp32"
-                                    + (" (BASELINE configs[4] per GPU: 2^20 envs over 8 GPUs)"
-                                       if args.envs == HEADLINE_ENVS else "")
-                                    if args.task == "CaptureXY" else
-                                    f"USV_Virtual_{args.task} num_envs={args.envs}/GPU PPO-MLP fp32")
-                       + (" [mixed_precision: bf16 GEMMs]" if args.mixed_precision else ""),
-                       "num_envs_per_gpu": args.envs, "horizon_length": agent.horizon_length,
-                       "minibatch_size": agent.minibatch_size, "mini_epochs": agent.mini_epochs_num,
-                       "parallelism": f"dp{world}", "exchange": exchange},
+        out.update({
             "fps_step_inference": play_fps, "fps_step_env_only": env_fps,
             "roofline": {"bound": "hbm", "kernel": step_kernel,
                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
@@ -569,7 +665,7 @@ def main():
                                          first_full_meter=first_full or None, milestones=miles,
                                          last100_mean_at_end=float(agent.game_rewards.get_mean())),
             "extra": dict(phase, **(dp_extra if world > 1 else {})),
-        }
+        })
         if sustained is not None:
             out["sustained"] = sustained
         tf = os.path.join(ROOT, "profiles", f"env_step_traffic_{args.envs}.json")
@@ -671,6 +767,7 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":

@@ -1176,6 +1176,24 @@ def gen_ckpt811(torch, rows=64, seed=8):
     print("ckpt811: mus[0]", out["mus"][0], "values[0]", out["values"][0])
 
 
+def gen_ref_cfg():
+    """ref_cfg_resolved.json: what the reference's own train / TEST task yamls (unmodified) compose and resolve
+    to under the overrides tests/test_hydra_cfg_cpu.py uses -- the train params and the task dict.  The scene
+    replay's NPZ path (a file on the author's machine) is left out; no root key of config.yaml is recorded."""
+    import json
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    from omniisaacgymenvs_loop_amd.scripts.rlgames_train import build_config
+    ref = build_config({"cfg_dir": os.path.join(REF, "omniisaacgymenvs", "cfg"), **REF_CFG_OVERRIDES})
+    ref["task"]["env"]["scene_replay"].pop("npz_path", None)
+    out = {"overrides": REF_CFG_OVERRIDES, "task_name": ref["task_name"], "train_params": ref["train"]["params"],
+           "task": ref["task"]}
+    with open(os.path.join(OUT, "ref_cfg_resolved.json"), "w", encoding="utf-8") as f:
+        json.dump(out, f, indent=1, sort_keys=True, ensure_ascii=True)
+        f.write("\n")
+
+
+REF_CFG_OVERRIDES = {"num_envs": 1024, "seed": 7, "max_iterations": 11}
+
 STAT_NAMES = [
     "total_reward", "distance_reward", "alignment_reward", "heading_improve_reward",
     "potential_shaping_reward", "speed_reward", "angular_reward", "turn_hazard_penalty",
@@ -1212,6 +1230,7 @@ def main():
         "loopz_shuffle": lambda: gen_loopz(torch, sampling="shuffle"),
         "loopz_expert": lambda: gen_loopz(torch, expert=True),
         "ckpt811": lambda: gen_ckpt811(torch),
+        "ref_cfg": gen_ref_cfg,
     }
     for name, fn in jobs.items():
         if args.only and name not in args.only.split(","):

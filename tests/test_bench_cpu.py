@@ -93,3 +93,18 @@ def test_dp_fields_names_a_mixed_exchange():
             {"rank": 1, "exchange": "collective", "selftest": "fail"}]
     ex, extra = bench.dp_fields(recs)
     assert ex == "mixed: collective, peer" and extra["dp_selftest"] == {"0": "pass", "1": "fail"}
+
+
+def test_dump_row_sample_is_fixed_and_bounded():
+    """Above the row caps the dump keeps a fixed seeded sample: the same sorted, distinct rows on every call."""
+    np = pytest.importorskip("numpy")
+    bench = pytest.importorskip("bench")
+    assert bench._dump_rows(bench.DUMP_EXP_ROWS, bench.DUMP_EXP_ROWS) is None
+    r1 = bench._dump_rows(131072 * 16, bench.DUMP_EXP_ROWS)
+    r2 = bench._dump_rows(131072 * 16, bench.DUMP_EXP_ROWS)
+    np.testing.assert_array_equal(r1, r2)
+    assert len(r1) == bench.DUMP_EXP_ROWS and np.all(np.diff(r1) > 0) and r1[-1] < 131072 * 16
+    # the headline size's dump: per-env arrays whole, per-row arrays sampled; bytes per kept row of each group
+    env_bytes = bench.DUMP_ENV_ROWS * (33 + 1 + 8) * 4
+    exp_bytes = bench.DUMP_EXP_ROWS * ((33 + 2 + 2 + 2 + 6) * 4 + 8)
+    assert env_bytes + exp_bytes + 2 ** 20 <= bench.DUMP_BUDGET_BYTES

@@ -84,7 +84,7 @@ def test_shape_mismatch_raises():
 import os  # noqa: E402
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF_CKPT = "/root/reference/811_3.5刹车_____（复件）/last_USV_ep_5450_rew_38.54975.pth"
+REF_CKPT = os.path.join(GOLDEN, "ckpt811_last_USV_ep_5450_rew_38.54975.pth")   # the reference's file, as it is
 
 
 def ckpt811_dict(d):
@@ -102,7 +102,7 @@ def ckpt811_dict(d):
 
 def test_reference_checkpoint_key_set_and_dtypes(golden):
     """The 811 checkpoint's key set, shapes and dtypes (pinned in the fixture), read by load_checkpoint with
-    weights_only=True when the reference tree is present; its model maps onto the padded device vector and back
+    weights_only=True from the stored file itself; its model maps onto the padded device vector and back
     bit for bit."""
     d = golden("ckpt811.npz")
     assert [str(k) for k in d["top_keys"]] == ["model", "epoch", "optimizer", "frame", "last_mean_rewards",
@@ -115,14 +115,13 @@ def test_reference_checkpoint_key_set_and_dtypes(golden):
     assert keys[6:] == [k for k, _ in C.PARAM_LAYOUT]
     assert d["sd__" + C.W1_KEY].shape == (C.NH, 13) and d["sd__" + C.W1_KEY].dtype == np.float32
     assert d["sd__value_mean_std.count"].dtype == np.float64 and d["sd__value_mean_std.count"].shape == ()
-    if os.path.exists(REF_CKPT):
-        ck = C.load_checkpoint(REF_CKPT)
-        assert list(ck.keys()) == [str(k) for k in d["top_keys"]]
-        assert list(ck["model"].keys()) == keys
-        for k in keys:
-            t = ck["model"][k]
-            assert t.dtype == torch.from_numpy(np.array(d["sd__" + k])).dtype, k
-            np.testing.assert_array_equal(t.numpy(), d["sd__" + k])
+    ck = C.load_checkpoint(REF_CKPT)
+    assert list(ck.keys()) == [str(k) for k in d["top_keys"]]
+    assert list(ck["model"].keys()) == keys
+    for k in keys:
+        t = ck["model"][k]
+        assert t.dtype == torch.from_numpy(np.array(d["sd__" + k])).dtype, k
+        np.testing.assert_array_equal(t.numpy(), d["sd__" + k])
     sd = ckpt811_dict(d)["model"]
     params = torch.zeros(C.NPARAM)
     obs_rms = torch.zeros(2 * C.NIN + 1, dtype=torch.float64)

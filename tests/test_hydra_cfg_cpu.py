@@ -8,8 +8,10 @@ import pytest
 from omniisaacgymenvs_loop_amd.tasks.usv_config import build_usv_cfg
 from omniisaacgymenvs_loop_amd.utils import hydra_cfg as HC
 
-REF_CFG = "/root/reference/omniisaacgymenvs/cfg"
-CFG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "omniisaacgymenvs_loop_amd", "cfg")
+# what the reference's own unmodified train / task yamls compose and resolve to (tests/golden/make_golden.py
+# gen_ref_cfg: build_config on the reference's cfg tree under the fixture's overrides)
+REF_RESOLVED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_cfg_resolved.json")
+CFG =os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "omniisaacgymenvs_loop_amd", "cfg")
 
 
 def test_relative_absolute_and_resolvers():
@@ -52,14 +54,17 @@ def test_cycle_is_an_error():
         HC.resolve({"a": "${b}", "b": "${a}"})
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference cfg tree not present")
 def test_reference_yamls_unmodified():
-    """The reference's own USV_PPOcontinuous_MLP.yaml and TEST task yaml, composed and resolved, give the
-    packaged configs' values on every key the hot path reads (the packaged task yaml only turns scene
-    replay off: the reference's NPZ path is a file on its author's machine)."""
+    """The reference's own USV_PPOcontinuous_MLP.yaml and TEST task yaml, composed and resolved (recorded in the
+    fixture from the unmodified files), give the packaged configs' values on every key the hot path reads (the
+    packaged task yaml only turns scene replay off: the reference's NPZ path is a file on its author's machine)."""
+    import json
     from omniisaacgymenvs_loop_amd.scripts.rlgames_train import build_config
-    ref = build_config({"cfg_dir": REF_CFG, "num_envs": 1024, "seed": 7, "max_iterations": 11})
-    ours = build_config({"num_envs": 1024, "seed": 7, "max_iterations": 11})
+    with open(REF_RESOLVED, encoding="utf-8") as f:
+        rec = json.load(f)
+    assert rec["overrides"] == {"num_envs": 1024, "seed": 7, "max_iterations": 11}
+    ref = {"train": {"params": rec["train_params"]}, "task": rec["task"], "task_name": rec["task_name"]}
+    ours = build_config(dict(rec["overrides"]))
     pr, po = ref["train"]["params"], ours["train"]["params"]
     assert pr["seed"] == 7 and pr["load_checkpoint"] is False and pr["load_path"] == ""
     assert pr["config"]["name"] == "USV" and pr["config"]["full_experiment_name"] == "USV"

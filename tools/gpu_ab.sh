@@ -14,8 +14,8 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   [ $rc -ne 0 ] && exit $rc
 fi
 for rep in 1 2; do
-  USV_HIP_LIB=${LIB_A:-} timeout -k 10 600 python3 bench.py --no-cpu-baseline ${BENCH_A_ARGS:-} > $O/a$rep.json 2> $O/a$rep.err || exit $?
-  USV_HIP_LIB=${LIB_B:-} timeout -k 10 600 python3 bench.py --no-cpu-baseline ${BENCH_B_ARGS:-} > $O/b$rep.json 2> $O/b$rep.err || exit $?
+  USV_HIP_LIB=${LIB_A:-} timeout -k 10 600 python3 bench.py --full --no-cpu-baseline ${BENCH_A_ARGS:-} > $O/a$rep.json 2> $O/a$rep.err || exit $?
+  USV_HIP_LIB=${LIB_B:-} timeout -k 10 600 python3 bench.py --full --no-cpu-baseline ${BENCH_B_ARGS:-} > $O/b$rep.json 2> $O/b$rep.err || exit $?
 done
 python3 - <<'PY'
 import json, os

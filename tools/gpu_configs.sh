@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/configs
 mkdir -p $O
 cd $R
-A="--steps 3 --warmup 2 --no-cpu-baseline --c2-steps 0"
+A="--full --steps 3 --warmup 2 --no-cpu-baseline --c2-steps 0"
 timeout -k 10 300 python3 bench.py --envs 65536 $A > $O/c3_65536.json 2> $O/c3.err || exit $?
 timeout -k 10 300 python3 bench.py --task GoToPose --envs 65536 $A > $O/c4_pose_65536.json 2> $O/c4p.err || exit $?
 timeout -k 10 300 python3 bench.py --task TrackXYOVelocity --envs 65536 $A > $O/c4_track_65536.json 2> $O/c4t.err || exit $?

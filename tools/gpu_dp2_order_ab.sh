@@ -18,7 +18,7 @@ for rep in $(seq 1 ${REPS:-2}); do
     LIB=""; [ $V != order3 ] && LIB=libusv_dp$V.so
     USV_HIP_LIB=$LIB timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
       --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps ${STEPS:-5} --warmup 1 --envs ${ENVS:-32768} \
-      --no-cpu-baseline --c2-steps 0 --milestone-seconds 0 > $O/dp2_${V}_$rep.json 2> $O/dp2_${V}_$rep.err \
+      --full --no-cpu-baseline --c2-steps 0 --milestone-seconds 0 > $O/dp2_${V}_$rep.json 2> $O/dp2_${V}_$rep.err \
       || { tail -30 $O/dp2_${V}_$rep.err; exit 1; }
     python3 -c "import json;d=json.loads(open('$O/dp2_${V}_$rep.json').read().strip().split('\n')[-1]);e=d['extra'];print('$V $rep', 'value %.4gM' % (d['value']/1e6), 'update_us/mb %.2f' % e['update_us_per_minibatch'], 'ppo pair us %.2f' % (d['roofline_ppo']['launch_ms']*1e3))"
   done

@@ -9,7 +9,7 @@ timeout -k 10 900 python3 -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1
 rc=$?
 tail -5 $O/pytest.log
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 600 python3 bench.py ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err
+timeout -k 10 600 python3 bench.py --full ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err
 rc=$?
 cat $O/bench.json
 exit $rc

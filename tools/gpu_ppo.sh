@@ -13,11 +13,11 @@ timeout -k 10 600 python3 -u -m pytest tests/test_ppo_gpu.py tests/test_train_gp
 rc=$?
 tail -3 $O/pytest.log
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 400 python3 bench.py --no-cpu-baseline --c2-steps 0 ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || exit $?
+timeout -k 10 400 python3 bench.py --full --no-cpu-baseline --c2-steps 0 ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || exit $?
 python3 -c "import json;d=json.load(open('$O/bench.json'));print(d['value'],d['ms_per_step'],d['extra'],d['roofline_ppo'])"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o trace -- \
-  python3 $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --c2-steps 0 > $O/prof.log 2>&1 || exit $?
+  python3 $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --c2-steps 0 > $O/prof.log 2>&1 || exit $?
 KS=$(find $O/prof -name "*kernel_stats.csv" | head -1)
 python3 $R/tools/kstats.py "$KS" 20
 exit 0

@@ -14,7 +14,7 @@ tail -5 $O/pytest_gpu.log
 cp gpurun_out/parity_errors.json $O/ 2>/dev/null
 [ $rc -ne 0 ] && exit $rc
 if [ "${BENCH:-1}" != "0" ]; then
-  timeout -k 10 600 python3 bench.py --no-cpu-baseline --steps ${STEPS:-10} ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err
+  timeout -k 10 600 python3 bench.py --full --no-cpu-baseline --steps ${STEPS:-10} ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err
   rc=$?
   tail -2 $O/bench.err
   python3 -c "import json;d=json.load(open('$O/bench.json'));print(d['value'],d['ms_per_step'],d['extra'].get('update_us_per_minibatch'),d['roofline']['frac'],d['roofline_ppo']['frac'])"
