@@ -504,6 +504,108 @@ int usv_hydrostatics(const usv_hydro_t *h, int n, const float *quat, const float
                      float *euler, float *wrench, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Batched policy evaluation (scripts/rlgames_play_loopz.py:305-433, 493-501, */
+/* 1046-1073, 1144-1321: the per-episode eval record, for every env at once)  */
+/* ------------------------------------------------------------------------ */
+
+/* rows of usv_eval_t.acc ([USV_EVA_ROWS][n] doubles: the running episode of each env; the float32 and integer
+ * quantities are held exactly) */
+#define USV_EVA_START_X   0   /* spawn, taken by usv_eval_mark before the first step (play_loopz.py:1152-1155) */
+#define USV_EVA_START_Y   1
+#define USV_EVA_GOAL_X    2
+#define USV_EVA_GOAL_Y    3
+#define USV_EVA_PREV_X    4   /* prev_pos of the path length */
+#define USV_EVA_PREV_Y    5
+#define USV_EVA_PREV_A0   6   /* prev_action0 */
+#define USV_EVA_PREV_A1   7
+#define USV_EVA_HAS_PREV  8
+#define USV_EVA_DSUM      9   /* action_delta_sum */
+#define USV_EVA_DCOUNT   10   /* action_delta_count */
+#define USV_EVA_SAT      11   /* sat_count (sat_total = 2 x steps) */
+#define USV_EVA_STEPS    12
+#define USV_EVA_RET      13   /* ep_return_raw */
+#define USV_EVA_PATH     14   /* path_length */
+#define USV_EVA_MIN_OBS  15   /* smallest obstacle distance of the episode's steps so far (+inf before the first) */
+#define USV_EVA_ROWS     16
+
+/* rows of usv_eval_t.episodes ([USV_EV_ROWS][max_episodes * n] doubles): episode k of env e is column k * n + e */
+#define USV_EV_SUCCESS        0   /* reason == goal_tolerance */
+#define USV_EV_REASON         1   /* USV_EV_REASON_* */
+#define USV_EV_LEN_STEPS      2
+#define USV_EV_TIME_TO_GOAL   3   /* steps x control_dt, NaN unless success */
+#define USV_EV_RETURN         4
+#define USV_EV_PATH_LENGTH    5
+#define USV_EV_STRAIGHT       6   /* |goal - start| */
+#define USV_EV_PATH_EFF       7   /* straight / max(path_length, 1e-6) */
+#define USV_EV_SMOOTH_MEAN    8   /* action_delta_sum / count, NaN for a one-step episode */
+#define USV_EV_SMOOTH_SUM     9
+#define USV_EV_SAT_RATE      10
+#define USV_EV_COLLISION     11   /* min_obs_dist < collision_threshold at the end */
+#define USV_EV_OOB           12   /* dist_to_goal > kill_dist at the end */
+#define USV_EV_IN_TOL        13   /* dist_to_goal < position_tolerance at the end */
+#define USV_EV_DIST_TO_GOAL  14
+#define USV_EV_START_X       15
+#define USV_EV_START_Y       16
+#define USV_EV_GOAL_X        17
+#define USV_EV_GOAL_Y        18
+#define USV_EV_END_X         19
+#define USV_EV_END_Y         20
+#define USV_EV_END_YAW       21
+#define USV_EV_MIN_OBS_END   22   /* float32, as _compute_step_metrics */
+#define USV_EV_MIN_OBS_EP    23   /* the smallest over the episode's steps */
+#define USV_EV_SCENE_IDX     24   /* usv_bufs_t.scene_last[e], -1 without scene replay */
+#define USV_EV_ENV_SUCC      25   /* the env's own done_succ / done_coll at the end */
+#define USV_EV_ENV_COLL      26
+#define USV_EV_SMOOTH_COUNT  27
+#define USV_EV_SAT_COUNT     28
+#define USV_EV_ROWS          29
+
+/* _infer_done_reason's priority order (play_loopz.py:493-501) */
+#define USV_EV_REASON_COLLISION 0
+#define USV_EV_REASON_OOB       1
+#define USV_EV_REASON_GOAL      2
+#define USV_EV_REASON_OTHER     3
+
+/* usv_eval_summary's output ([USV_EVS_N] doubles).  The six metrics of _summarize_eval (play_loopz.py:1052-1059),
+ * in its order, each as (finite count, mean, population std) from USV_EVS_METRICS */
+#define USV_EVS_EPISODES   0   /* filled records */
+#define USV_EVS_DROPPED    1   /* finished episodes past max_episodes per env (counted, not kept) */
+#define USV_EVS_REASONS    2   /* 4 counts, USV_EV_REASON_* order */
+#define USV_EVS_COLLISION  6
+#define USV_EVS_OOB        7
+#define USV_EVS_METRICS    8   /* success, time_to_goal_sec, path_efficiency, action_smoothness_mean,
+                                  action_saturation_rate, return_raw */
+#define USV_EVS_NMETRIC    6
+#define USV_EVS_N         26
+
+typedef struct usv_eval {
+  double  *acc;          /* [USV_EVA_ROWS][n] */
+  double  *episodes;     /* [USV_EV_ROWS][max_episodes * n] */
+  int32_t *ep_count;     /* [n] finished episodes of each env, the ones past max_episodes included */
+  int32_t max_episodes;  /* K >= 1: records kept per env */
+  float   action_scale;  /* saturation: |a_i| > float32(0.95 * action_scale) (play_loopz.py:805, 1235) */
+  double  control_dt;    /* simulated seconds per env step: sim.dt x controlFrequencyInv (play_loopz.py:911-920)
+                            = usv_cfg_t.dt x usv_cfg_t.substeps */
+} usv_eval_t;
+
+/* CaptureXY only (the record needs obstacles): another cfg->task_kind is status 3.  Status 1: a NULL argument or
+ * buffer, n <= 0; status 2: max_episodes < 1 or max_episodes * n past 2^31 - 1.  All checks precede device work.
+ * One thread per env, no atomics: every result is independent of scheduling. */
+/* zero the accumulators, the episode table and the per-env episode counts (so nothing is dropped) */
+int usv_eval_begin(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_eval_t *ev, void *stream);
+/* between usv_reset (+ usv_potential_field) and usv_env_step: every env with just_reset != 0 starts an episode
+ * (spawn and goal snapshot, prev-pos = spawn, accumulators and the previous action cleared) */
+int usv_eval_mark(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_eval_t *ev, void *stream);
+/* after usv_env_step, with the actions [n][2] that step consumed: accumulate the step; an env with
+ * reset_buf != 0 finishes its episode into column ep_count[e] * n + e (while ep_count[e] < max_episodes) */
+int usv_eval_step(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_eval_t *ev, const float *actions,
+                  void *stream);
+/* out [USV_EVS_N] (device): counts and, per metric, the count, mean and population standard deviation of the
+ * finite values of the filled records (NaN mean / std when there is none), two passes in double in a fixed
+ * order: the same table gives the same bits */
+int usv_eval_summary(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_eval_t *ev, double *out, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* PPO entry points (rl_games a2c_continuous / a2c_common)                   */
 /* ------------------------------------------------------------------------ */
 

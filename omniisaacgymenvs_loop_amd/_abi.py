@@ -88,6 +88,10 @@ class UsvHydro(ctypes.Structure):
     _fields_ = _struct_fields(_TXT, "usv_hydro", DEFINES)
 
 
+class UsvEval(ctypes.Structure):
+    _fields_ = _struct_fields(_TXT, "usv_eval", DEFINES)
+
+
 class LzCfg(ctypes.Structure):
     _fields_ = _struct_fields(_TXT, "lz_cfg", DEFINES)
 
@@ -131,10 +135,10 @@ PEN = enum_values("usv_pen_kind")
 # usv_hip_layout_key(); _capi.lib() refuses a library whose key differs from layout_key() here, so a
 # library built from another header -- a moved slab row, a resized buffer, a reordered struct --
 # fails loudly before its first call instead of addressing past a buffer.
-LAYOUT_STRUCTS = ("usv_cfg", "usv_bufs", "usv_hydro", "ppo_cfg", "ppo_adam_banks", "ppo_dp", "lz_cfg")
+LAYOUT_STRUCTS = ("usv_cfg", "usv_bufs", "usv_hydro", "usv_eval", "ppo_cfg", "ppo_adam_banks", "ppo_dp", "lz_cfg")
 LAYOUT_ENUMS = ("usv_stat_key", "usv_pen_kind", "usv_dist_row")
-_STRUCT_CLASSES = {"usv_cfg": UsvCfg, "usv_bufs": UsvBufs, "usv_hydro": UsvHydro, "ppo_cfg": PpoCfg,
-                   "ppo_adam_banks": PpoAdamBanks, "ppo_dp": PpoDp, "lz_cfg": LzCfg}
+_STRUCT_CLASSES = {"usv_cfg": UsvCfg, "usv_bufs": UsvBufs, "usv_hydro": UsvHydro, "usv_eval": UsvEval,
+                   "ppo_cfg": PpoCfg, "ppo_adam_banks": PpoAdamBanks, "ppo_dp": PpoDp, "lz_cfg": LzCfg}
 GUARD_DEFINES = ("USV_HIP_H",)
 
 

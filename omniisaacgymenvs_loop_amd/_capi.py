@@ -13,7 +13,7 @@ import subprocess
 
 import torch  # noqa: F401  -- load torch's HIP runtime first; the .so binds to it (same SONAME)
 
-from ._abi import PpoCfg, UsvBufs, UsvCfg
+from ._abi import PpoCfg, UsvBufs, UsvCfg, UsvEval
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -21,7 +21,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libusv_hip.so")
 # instrumented build (per-workgroup phase timestamps, tools/phase_probe.py); selected with USV_HIP_PROBE=1
 PROBE_LIB_PATH = os.path.join(LIB_DIR, "libusv_hip_probe.so")
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("usv_env.hip", "usv_field.hip", "ppo.hip", "loopz.hip")]
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("usv_env.hip", "usv_field.hip", "usv_eval.hip", "ppo.hip", "loopz.hip")]
 DEPS = SOURCES + [os.path.join(HERE, "csrc", "usv_device.h"), os.path.join(HERE, "csrc", "usv_layout_gen.h"),
                   os.path.join(ROOT, "include", "usv_hip.h")]
 
@@ -63,6 +63,10 @@ def _declare(lib):
         "usv_env_step_part": [P, P, P, P, F, U64, U64, P, I, P],
         "usv_forces": [P, P, P, P],
         "usv_hydrostatics": [P, I, P, P, P, P, P, P],
+        "usv_eval_begin": [P, P, P, P],
+        "usv_eval_mark": [P, P, P, P],
+        "usv_eval_step": [P, P, P, P, P],
+        "usv_eval_summary": [P, P, P, P, P],
         "lz_act": [P, P, P, I, P, P, P, P, P, U64, U64, P, P],
         "lz_value": [P, P, P, P, P],
         "lz_store": [P, P, P, I, P, P, P],
@@ -157,4 +161,4 @@ def byref(s):
     return ctypes.byref(s)
 
 
-__all__ = ["build", "lib", "call", "call_rc", "ptr", "stream_ptr", "byref", "UsvCfg", "UsvBufs", "PpoCfg", "LIB_PATH"]
+__all__ = ["build", "lib", "call", "call_rc", "ptr", "stream_ptr", "byref", "UsvCfg", "UsvBufs", "UsvEval", "PpoCfg", "LIB_PATH"]

@@ -114,6 +114,65 @@
   X(USV_SLAB_TGT_H, "USV_SLAB_TGT_H") \
   X(USV_SLAB_STALE, "USV_SLAB_STALE") \
   X(USV_SLAB_ROWS, "USV_SLAB_ROWS") \
+  X(USV_EVA_START_X, "USV_EVA_START_X") \
+  X(USV_EVA_START_Y, "USV_EVA_START_Y") \
+  X(USV_EVA_GOAL_X, "USV_EVA_GOAL_X") \
+  X(USV_EVA_GOAL_Y, "USV_EVA_GOAL_Y") \
+  X(USV_EVA_PREV_X, "USV_EVA_PREV_X") \
+  X(USV_EVA_PREV_Y, "USV_EVA_PREV_Y") \
+  X(USV_EVA_PREV_A0, "USV_EVA_PREV_A0") \
+  X(USV_EVA_PREV_A1, "USV_EVA_PREV_A1") \
+  X(USV_EVA_HAS_PREV, "USV_EVA_HAS_PREV") \
+  X(USV_EVA_DSUM, "USV_EVA_DSUM") \
+  X(USV_EVA_DCOUNT, "USV_EVA_DCOUNT") \
+  X(USV_EVA_SAT, "USV_EVA_SAT") \
+  X(USV_EVA_STEPS, "USV_EVA_STEPS") \
+  X(USV_EVA_RET, "USV_EVA_RET") \
+  X(USV_EVA_PATH, "USV_EVA_PATH") \
+  X(USV_EVA_MIN_OBS, "USV_EVA_MIN_OBS") \
+  X(USV_EVA_ROWS, "USV_EVA_ROWS") \
+  X(USV_EV_SUCCESS, "USV_EV_SUCCESS") \
+  X(USV_EV_REASON, "USV_EV_REASON") \
+  X(USV_EV_LEN_STEPS, "USV_EV_LEN_STEPS") \
+  X(USV_EV_TIME_TO_GOAL, "USV_EV_TIME_TO_GOAL") \
+  X(USV_EV_RETURN, "USV_EV_RETURN") \
+  X(USV_EV_PATH_LENGTH, "USV_EV_PATH_LENGTH") \
+  X(USV_EV_STRAIGHT, "USV_EV_STRAIGHT") \
+  X(USV_EV_PATH_EFF, "USV_EV_PATH_EFF") \
+  X(USV_EV_SMOOTH_MEAN, "USV_EV_SMOOTH_MEAN") \
+  X(USV_EV_SMOOTH_SUM, "USV_EV_SMOOTH_SUM") \
+  X(USV_EV_SAT_RATE, "USV_EV_SAT_RATE") \
+  X(USV_EV_COLLISION, "USV_EV_COLLISION") \
+  X(USV_EV_OOB, "USV_EV_OOB") \
+  X(USV_EV_IN_TOL, "USV_EV_IN_TOL") \
+  X(USV_EV_DIST_TO_GOAL, "USV_EV_DIST_TO_GOAL") \
+  X(USV_EV_START_X, "USV_EV_START_X") \
+  X(USV_EV_START_Y, "USV_EV_START_Y") \
+  X(USV_EV_GOAL_X, "USV_EV_GOAL_X") \
+  X(USV_EV_GOAL_Y, "USV_EV_GOAL_Y") \
+  X(USV_EV_END_X, "USV_EV_END_X") \
+  X(USV_EV_END_Y, "USV_EV_END_Y") \
+  X(USV_EV_END_YAW, "USV_EV_END_YAW") \
+  X(USV_EV_MIN_OBS_END, "USV_EV_MIN_OBS_END") \
+  X(USV_EV_MIN_OBS_EP, "USV_EV_MIN_OBS_EP") \
+  X(USV_EV_SCENE_IDX, "USV_EV_SCENE_IDX") \
+  X(USV_EV_ENV_SUCC, "USV_EV_ENV_SUCC") \
+  X(USV_EV_ENV_COLL, "USV_EV_ENV_COLL") \
+  X(USV_EV_SMOOTH_COUNT, "USV_EV_SMOOTH_COUNT") \
+  X(USV_EV_SAT_COUNT, "USV_EV_SAT_COUNT") \
+  X(USV_EV_ROWS, "USV_EV_ROWS") \
+  X(USV_EV_REASON_COLLISION, "USV_EV_REASON_COLLISION") \
+  X(USV_EV_REASON_OOB, "USV_EV_REASON_OOB") \
+  X(USV_EV_REASON_GOAL, "USV_EV_REASON_GOAL") \
+  X(USV_EV_REASON_OTHER, "USV_EV_REASON_OTHER") \
+  X(USV_EVS_EPISODES, "USV_EVS_EPISODES") \
+  X(USV_EVS_DROPPED, "USV_EVS_DROPPED") \
+  X(USV_EVS_REASONS, "USV_EVS_REASONS") \
+  X(USV_EVS_COLLISION, "USV_EVS_COLLISION") \
+  X(USV_EVS_OOB, "USV_EVS_OOB") \
+  X(USV_EVS_METRICS, "USV_EVS_METRICS") \
+  X(USV_EVS_NMETRIC, "USV_EVS_NMETRIC") \
+  X(USV_EVS_N, "USV_EVS_N") \
   X(PPO_NIN, "PPO_NIN") \
   X(PPO_NH, "PPO_NH") \
   X(PPO_NA, "PPO_NA") \
@@ -418,6 +477,13 @@
   X(offsetof(usv_hydro_t, waterplane_area), "usv_hydro.waterplane_area") \
   X(offsetof(usv_hydro_t, zero_height), "usv_hydro.zero_height") \
   X(offsetof(usv_hydro_t, max_volume), "usv_hydro.max_volume") \
+  X(sizeof(usv_eval_t), "sizeof usv_eval") \
+  X(offsetof(usv_eval_t, acc), "usv_eval.acc") \
+  X(offsetof(usv_eval_t, episodes), "usv_eval.episodes") \
+  X(offsetof(usv_eval_t, ep_count), "usv_eval.ep_count") \
+  X(offsetof(usv_eval_t, max_episodes), "usv_eval.max_episodes") \
+  X(offsetof(usv_eval_t, action_scale), "usv_eval.action_scale") \
+  X(offsetof(usv_eval_t, control_dt), "usv_eval.control_dt") \
   X(sizeof(ppo_cfg_t), "sizeof ppo_cfg") \
   X(offsetof(ppo_cfg_t, horizon), "ppo_cfg.horizon") \
   X(offsetof(ppo_cfg_t, n_envs), "ppo_cfg.n_envs") \

@@ -76,6 +76,19 @@ class PpoPlayerContinuous:
             return torch.clamp(sc["mu"], -1.0, 1.0)     # players.py:139-150: current_action = mu, clamped
         return self._actions
 
+    def evaluate(self, episodes_per_env: int = 1, max_steps=None):
+        """Play deterministically (clamp(mu, -1, 1), as get_action) until every env has finished
+        `episodes_per_env` episodes or `max_steps` env steps were taken, with the per-episode records kept on
+        the device (eval.EpisodeEvaluator); returns (episodes: dict of numpy arrays, one entry per finished
+        episode; summary: dict).  No per-step host sync: completion is one small read-back every
+        eval.evaluator.CHECK_EVERY steps."""
+        from ..eval import EpisodeEvaluator, rollout
+        task = self.env._task
+        ev = EpisodeEvaluator(task, episodes_per_env=episodes_per_env, action_scale=float(task.clip_actions))
+        rollout(task, lambda obs: self.get_action(obs, True), ev, max_steps=max_steps)
+        self.evaluator = ev
+        return ev.episodes(), ev.summary()
+
     def run(self):
         obs = self.env.reset()
         steps = torch.zeros(self.num_actors, device=self.device)

@@ -359,7 +359,7 @@ class USVVirtual:
 
     def env_step(self, actions: torch.Tensor, u_step: Optional[torch.Tensor] = None,
                  u_reset: Optional[torch.Tensor] = None, post_state: Optional[torch.Tensor] = None,
-                 overlap: bool = False, chain: bool = False, after_fork=None):
+                 overlap: bool = False, chain: bool = False, after_fork=None, evaluator=None):
         """pre_physics_step + 10 substeps + post_physics_step (USV_Virtual.py:1042-1652).
 
         Returns the device tensors (obs [n,33], rew [n], dones int64 [n]).  u_step / u_reset replay
@@ -370,7 +370,13 @@ class USVVirtual:
         overlap: the overlapped step (_step_overlapped); chain: this overlapped step directly follows one in the
         same sequence of calls (a rollout, or one captured graph), so its reset may run on the side stream.
         after_fork: a callable issuing work that reads the previous step's rew / dones, run on the current stream
-        before this step's env kernels write them (the default overlapped step: after the fields' fork)."""
+        before this step's env kernels write them (the default overlapped step: after the fields' fork).
+        evaluator: an eval.EpisodeEvaluator; the plain step then issues usv_eval_mark before usv_env_step and
+        usv_eval_step after it (None: no kernel is added).  The overlapped step has no point at which every
+        env's reward is final on one stream, so it refuses an evaluator."""
+        if evaluator is not None and overlap:
+            raise ValueError("env_step(overlap=True) cannot carry an evaluator: the rewards of the envs reset this "
+                             "step are final only after join_step(); use the plain step")
         actions = self._f32(actions)
         s = _capi.stream_ptr()
         cfg, b = _capi.byref(self.cfg), _capi.byref(self._bufs)
@@ -403,6 +409,8 @@ class USVVirtual:
             return self._step_overlapped(actions, bias, k, u_step, fold_late=fold_late, after_fork=after_fork)
         if self._has_field:   # CaptureXY only (GoToPose / TrackXYOVelocity have no obstacles)
             _capi.call("usv_potential_field", cfg, b, s)
+        if evaluator is not None:
+            evaluator.mark()   # the spawn: before the integration (or the recorded state that replaces it)
         substeps = self.cfg.substeps
         if post_state is not None:
             self.state.copy_(post_state.to(self._device, torch.float32).reshape(8, self._num_envs))
@@ -412,6 +420,8 @@ class USVVirtual:
                        self.seed, k, _capi.ptr(u_step), s)
         finally:
             self.cfg.substeps = substeps
+        if evaluator is not None:
+            evaluator.step(actions)
         return self.obs_view, self.rew_buf, self.dones
 
     def _step_overlapped(self, actions, bias, k, u_step, reset_on_side=False, fold_late=False, after_fork=None):
