@@ -905,6 +905,88 @@ int lz_enforce_min_std(const lz_cfg_t *cfg, float *params, void *stream);
 int lz_partials_floats(const lz_cfg_t *cfg);
 int lz_grad_floats(int obs_dim);
 
+/* ------------------------------------------------------------------------
+ * sysid: stage 2 of the reference's pipeline (scripts/dagger_usv_sysid_loopz.py with algo/ppo/dagger.py
+ * USVSysIDAgent / USVSysIDTrainer, module.py:392-448 StateHistoryEncoder(tsteps=50),
+ * envs/usv_raisim_vecenv.py:387-611 USVSysIDVecEnv).  The student encoder reads the last SY_T non-privileged
+ * observations (D = obs_dim - SY_PRIV floats each) and is regressed (MSE) onto the frozen teacher's latent
+ * z* = mass_encoder(priv tail); the student drives the env through the teacher's frozen action_mlp.
+ *
+ * Encoder parameters, flat in state_dict order (sysid_nparam(obs_dim) floats, 20,136 for obs_dim 33):
+ *   encoder.0.{weight [32][D], bias}, conv_layers.{0 [32][32][8], 2 [32][32][5], 4 [32][32][5]}.{weight, bias},
+ *   linear_output.0.{weight [8][96], bias}; LeakyReLU 0.01 after every layer.  The conv input (c, t) is element
+ *   c * SY_T + t of the row-major [SY_T][32] projection (the reference's raw reshape, not a transpose).
+ * Teacher parameters: the actor's `architecture` state dict flat in key order (loopz layout above:
+ *   mass_encoder.{0,2,4}, action_mlp.{0,2,4}).
+ *
+ * Frame stream: a ring of R = SY_T - 1 + horizon frames, stream [R][n][D].  Update u has base = (u * horizon) % R;
+ * the window of storage row (s, env), s in [0, horizon), is the SY_T ring slots (base + s + k) % R, k = 0..SY_T-1,
+ * the last one the observation the action of step s is computed from.  Flattened windows are never stored.
+ * valid_rows [horizon][n] (int32): the number of trailing frames of the row's window that are its own; a position
+ * k < SY_T - valid reads the frame of position SY_T - valid instead (fill_history_on_reset = "repeat": a reset
+ * fills the whole window with one frame).  In "zeros" mode valid is always SY_T: the frames before a reset() are
+ * the zeros the host clears the stream to, and a done env's window slides on across the episode boundary, as the
+ * reference's does.
+ * Status: 1 = NULL / out-of-range argument, 2 = unsupported configuration (history_len != SY_T, obs_dim outside
+ * 33..LZ_MAX_OBS).
+ * ------------------------------------------------------------------------ */
+#define SY_T      50
+#define SY_PRIV   8
+#define SY_LAT    8
+#define SY_CH     32
+#define SY_K1     8
+#define SY_S1     4
+#define SY_L1     11
+#define SY_K2     5
+#define SY_L2     7
+#define SY_L3     3
+#define SY_FILL_ZEROS  0
+#define SY_FILL_REPEAT 1
+/* sysid_metrics' output ([SY_MET_N] doubles) */
+#define SY_MET_MSE       0   /* mean of the last `mini_batches` loss slots */
+#define SY_MET_ZSTAR_VAR 1   /* population variance per dimension, mean over dimensions */
+#define SY_MET_ZHAT_VAR  2
+#define SY_MET_R2_TOTAL  3   /* 1 - sum sse / (sum sst + 1e-8) */
+#define SY_MET_R2_DIM    4   /* [SY_LAT] 1 - sse_i / (sst_i + 1e-8) */
+#define SY_MET_SSE       12  /* [SY_LAT] */
+#define SY_MET_SST       20  /* [SY_LAT] */
+#define SY_MET_N         28
+
+/* floats of the flat encoder parameter vector; <= 0 for an unsupported obs_dim */
+int sysid_nparam(int obs_dim);
+/* floats of the partial-gradient scratch of sysid_minibatch for minibatches of up to `rows` rows */
+int sysid_partials_floats(int obs_dim, int rows);
+/* Step s of an update, before the action: writes obs[:, :D] ([n][obs_dim], the observation of this step) to ring
+ * slot (base + s + SY_T - 1) % R, zstar[s] = teacher mass_encoder(obs[:, D:]) ([horizon][n][SY_LAT]) and
+ * valid_rows[s]: "zeros" mode SY_T; "repeat" mode 1 where fresh != 0 or dones[env] != 0 (dones [n] int64 of
+ * the env step that produced obs; NULL = none), else min(valid_cur + 1, SY_T).  valid_cur [n] carries over.
+ * teacher = NULL: no z* (a student that only keeps its history). */
+int sysid_append(const float *obs, const int64_t *dones, const float *teacher, int n, int obs_dim, int history_len,
+                 int horizon, int base, int s, int fill_mode, int fresh, float *stream, int32_t *valid_rows,
+                 int32_t *valid_cur, float *zstar, void *stream_);
+/* Encoder forward on storage rows [row0, row0 + rows) (row = s * n + env): zhat [rows][SY_LAT]. */
+int sysid_encode(const float *enc, int n, int obs_dim, int history_len, int horizon, int base, int row0, int rows,
+                 const float *stream, const int32_t *valid_rows, float *zhat, void *stream_);
+/* Student step s: zhat [n][SY_LAT] = encoder(window), actions [n][LZ_NA] = tanh action_mlp([cur | zhat]). */
+int sysid_student_step(const float *enc, const float *teacher, int n, int obs_dim, int history_len, int horizon,
+                       int base, int s, const float *stream, const int32_t *valid_rows, float *zhat, float *actions,
+                       void *stream_);
+/* One Adam step on rows [row0, row0 + rows): forward + backward of the encoder, MSE (mean over rows x SY_LAT)
+ * against zstar, per-workgroup partial gradients folded in a fixed order into grad [sysid_nparam] by the kernel that
+ * applies torch.optim.Adam (betas 0.9 / 0.999, eps 1e-8; adam_step = 1-based step count); *loss_out (device) =
+ * the minibatch loss.  apply = 0: gradient and loss only. */
+int sysid_minibatch(float *enc, float *adam_m, float *adam_v, int n, int obs_dim, int history_len, int horizon,
+                    int base, int row0, int rows, float lr, int adam_step, int apply, const float *stream,
+                    const int32_t *valid_rows, const float *zstar, float *partials, float *grad, float *loss_out,
+                    void *stream_);
+/* USVSysIDTrainer.update's diagnostics over all horizon x n rows with the given encoder, in double, every sum in
+ * a fixed order: out [SY_MET_N]; losses [n_losses] the per-minibatch loss slots (mse = mean of the last
+ * mini_batches); scratch: zhat_work [horizon * n][SY_LAT] floats, work sysid_metrics_work_doubles() doubles. */
+int sysid_metrics_work_doubles(void);
+int sysid_metrics(const float *enc, int n, int obs_dim, int history_len, int horizon, int base, const float *stream,
+                  const int32_t *valid_rows, const float *zstar, const float *losses, int n_losses, int mini_batches,
+                  float *zhat_work, double *work, double *out, void *stream_);
+
 /* library version */
 int usv_hip_version(void);
 /* the layout this library was compiled with: every object-like integer #define of this header (except the

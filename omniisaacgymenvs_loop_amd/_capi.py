@@ -21,7 +21,8 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libusv_hip.so")
 # instrumented build (per-workgroup phase timestamps, tools/phase_probe.py); selected with USV_HIP_PROBE=1
 PROBE_LIB_PATH = os.path.join(LIB_DIR, "libusv_hip_probe.so")
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("usv_env.hip", "usv_field.hip", "usv_eval.hip", "ppo.hip", "loopz.hip")]
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("usv_env.hip", "usv_field.hip", "usv_eval.hip", "ppo.hip", "loopz.hip",
+                                                    "usv_sysid.hip")]
 DEPS = SOURCES + [os.path.join(HERE, "csrc", "usv_device.h"), os.path.join(HERE, "csrc", "usv_layout_gen.h"),
                   os.path.join(ROOT, "include", "usv_hip.h")]
 
@@ -98,6 +99,14 @@ def _declare(lib):
         "lz_grad_floats": [I],
         "lz_partials_floats": [P],
         "ppo_meter_floats": [I, I],
+        "sysid_nparam": [I],
+        "sysid_partials_floats": [I, I],
+        "sysid_append": [P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P],
+        "sysid_encode": [P, I, I, I, I, I, I, I, P, P, P, P],
+        "sysid_student_step": [P, P, I, I, I, I, I, I, P, P, P, P, P],
+        "sysid_minibatch": [P, P, P, I, I, I, I, I, I, I, F, I, I, P, P, P, P, P, P, P],
+        "sysid_metrics": [P, I, I, I, I, I, P, P, P, P, I, I, P, P, P, P],
+        "sysid_metrics_work_doubles": [],
         "usv_hip_version": [],
         "usv_hip_layout_key": [],   # (restype long long, below)
     }

@@ -194,6 +194,26 @@
   X(LZ_NH, "LZ_NH") \
   X(LZ_NA, "LZ_NA") \
   X(LZ_MAX_OBS, "LZ_MAX_OBS") \
+  X(SY_T, "SY_T") \
+  X(SY_PRIV, "SY_PRIV") \
+  X(SY_LAT, "SY_LAT") \
+  X(SY_CH, "SY_CH") \
+  X(SY_K1, "SY_K1") \
+  X(SY_S1, "SY_S1") \
+  X(SY_L1, "SY_L1") \
+  X(SY_K2, "SY_K2") \
+  X(SY_L2, "SY_L2") \
+  X(SY_L3, "SY_L3") \
+  X(SY_FILL_ZEROS, "SY_FILL_ZEROS") \
+  X(SY_FILL_REPEAT, "SY_FILL_REPEAT") \
+  X(SY_MET_MSE, "SY_MET_MSE") \
+  X(SY_MET_ZSTAR_VAR, "SY_MET_ZSTAR_VAR") \
+  X(SY_MET_ZHAT_VAR, "SY_MET_ZHAT_VAR") \
+  X(SY_MET_R2_TOTAL, "SY_MET_R2_TOTAL") \
+  X(SY_MET_R2_DIM, "SY_MET_R2_DIM") \
+  X(SY_MET_SSE, "SY_MET_SSE") \
+  X(SY_MET_SST, "SY_MET_SST") \
+  X(SY_MET_N, "SY_MET_N") \
   X(ST_TOTAL_REWARD, "ST_TOTAL_REWARD") \
   X(ST_DISTANCE_REWARD, "ST_DISTANCE_REWARD") \
   X(ST_ALIGNMENT_REWARD, "ST_ALIGNMENT_REWARD") \
