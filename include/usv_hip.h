@@ -606,6 +606,73 @@ int usv_eval_step(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_eval_t *e
 int usv_eval_summary(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_eval_t *ev, double *out, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Scenario tables (scripts/build_usv_scenario_table.py: sampling :153-209,  */
+/* metrics :215-258; scripts/teacher_filter_scenario_table.py: the           */
+/* per-scenario aggregate :712-759 and the filter's verdict :512-552)        */
+/* ------------------------------------------------------------------------ */
+
+/* Philox sites of usv_scn_generate: ctr = {candidate lo, candidate hi, iteration, site}, key = seed.
+ * A word w is the uniform u = w / 2^32 (exact in double); a value is float32(lo + (hi - lo) * u), in double. */
+#define USV_SCN_SITE_POSE   0   /* iteration 0: target x, target y, spawn radius, spawn angle */
+#define USV_SCN_SITE_YAW    1   /* iteration 0: yaw, init vel x, init vel y */
+#define USV_SCN_SITE_OBST  16   /* + obstacle index; iteration 0 = first draw, k >= 1 = k-th redraw: x, y */
+#define USV_SCN_MAX_ITERS 4096  /* largest max_iterations accepted */
+#define USV_SCN_MAX_COUNT 67108864   /* largest count / S per call (2^26: every index fits 32 bits) */
+
+/* rows of usv_scn_metrics' output ([USV_SCM_ROWS][S] float32) */
+#define USV_SCM_D_SPAWN  0
+#define USV_SCM_D_GOAL   1
+#define USV_SCM_D_CORR   2
+#define USV_SCM_D_OO     3
+#define USV_SCM_DENSITY  4
+#define USV_SCM_ROWS     5
+
+/* the representative reason of a scenario whose rollouts succeed only in part (teacher_filter :727-728) */
+#define USV_EV_REASON_MIXED 4
+
+/* rows of usv_scn_fold's output ([USV_SCF_ROWS][S] doubles) */
+#define USV_SCF_PRESENT       0   /* rollouts with a record */
+#define USV_SCF_SUCCESS_RATE  1
+#define USV_SCF_COLL_RATE     2
+#define USV_SCF_OOB_RATE      3
+#define USV_SCF_COLL_ANY      4
+#define USV_SCF_OOB_ANY       5
+#define USV_SCF_REASON        6   /* USV_EV_REASON_*, MIXED included */
+#define USV_SCF_STEPS         7   /* trunc(mean steps) */
+#define USV_SCF_RETURN        8   /* mean ep_return_raw */
+#define USV_SCF_FINAL_DIST    9   /* mean final_dist_to_goal */
+#define USV_SCF_MIN_OBS      10   /* min over rollouts of min_obs_dist_episode */
+#define USV_SCF_MIN_MARGIN   11   /* min over rollouts of min_obs_dist_episode - collision_threshold */
+#define USV_SCF_VERDICT      12   /* USV_SCV_* */
+#define USV_SCF_DIFFICULTY   13
+#define USV_SCF_ROWS         14
+
+#define USV_SCV_KEEP        0
+#define USV_SCV_HARD_REJECT 1
+#define USV_SCV_EASY_REJECT 2
+#define USV_SCV_INCOMPLETE  3   /* a rollout of the scenario has no record: no verdict */
+
+/* Status 1: a NULL argument, count / S / n / R / K <= 0 or first < 0; status 2: a size past USV_SCN_MAX_COUNT,
+ * max_iterations outside [0, USV_SCN_MAX_ITERS], init_vel_mode not 0 / 1, K != ceil(S R / n) or K past the
+ * evaluator's max_episodes.  All checks precede device work. */
+/* count candidates first .. first + count - 1 of the sampling law (build_usv_scenario_table.py:153-209) on Philox:
+ * rows [count][USV_SCENE_STRIDE] (USV_SC_* layout, yaw = float32 of the drawn yaw, columns 39.. zero) and
+ * spawn_quat [count][4] (w, x, y, z).  16 lanes per candidate, one obstacle per lane; init_vel_mode 0 = zero,
+ * 1 = U(-1.5, 1.5)^2.  No dedup. */
+int usv_scn_generate(uint64_t seed, int64_t first, int count, double goal_random_position, double min_spawn_dist,
+                     double max_spawn_dist, double box_half_range, double min_dist_safe, int max_iterations,
+                     int init_vel_mode, float *rows, float *spawn_quat, void *stream);
+/* _compute_metrics (:215-258) of S scene rows, float32 in the reference's order: out [USV_SCM_ROWS][S].
+ * An obstacle counts when |x| < limbo_threshold and |y| < limbo_threshold; none: +inf in all five. */
+int usv_scn_metrics(const float *rows, int S, double obstacle_radius, double limbo_threshold, float *out,
+                    void *stream);
+/* the per-scenario aggregate of the evaluator's table: playlist row p = s R + r is column (p % K) n + p / K,
+ * present when p % K < min(ep_count[p / K], K).  out [USV_SCF_ROWS][S]; double sums in rollout order, one thread
+ * per scenario: the same table gives the same bits. */
+int usv_scn_fold(const usv_eval_t *ev, int n, int S, int R, int K, double collision_threshold, int easy_steps_max,
+                 double easy_margin_min, int max_steps, double *out, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* PPO entry points (rl_games a2c_continuous / a2c_common)                   */
 /* ------------------------------------------------------------------------ */
 
@@ -874,6 +941,10 @@ int lz_nparam(int obs_dim);
 int lz_act(const lz_cfg_t *cfg, const float *params, const float *obs, int t, float *st_obs, float *st_act,
            float *st_logp, float *st_val, float *actions_out, uint64_t seed, uint64_t step,
            const float *eps_inject, void *stream);
+/* the deterministic teacher (teacher_filter_scenario_table.py:446-450): actions_out [N][2] =
+ * tanh(architecture(obs)) * action_scale, architecture ending in its Tanh head.  No draw, no storage, no critic;
+ * params as lz_act's (only the actor net and std are read).  Bit-identical to lz_act with eps_inject all zeros. */
+int lz_play(const lz_cfg_t *cfg, const float *params, const float *obs, float *actions_out, void *stream);
 /* critic forward only: values [N] (ppo.update's last_values) */
 int lz_value(const lz_cfg_t *cfg, const float *params, const float *obs, float *values, void *stream);
 /* storage.add_transitions' rewards / dones at step t (nan_to_num on the reward) */

@@ -22,7 +22,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libusv_hip.so")
 # instrumented build (per-workgroup phase timestamps, tools/phase_probe.py); selected with USV_HIP_PROBE=1
 PROBE_LIB_PATH = os.path.join(LIB_DIR, "libusv_hip_probe.so")
 SOURCES = [os.path.join(HERE, "csrc", f) for f in ("usv_env.hip", "usv_field.hip", "usv_eval.hip", "ppo.hip", "loopz.hip",
-                                                    "usv_sysid.hip")]
+                                                    "usv_sysid.hip", "usv_scenario.hip")]
 DEPS = SOURCES + [os.path.join(HERE, "csrc", "usv_device.h"), os.path.join(HERE, "csrc", "usv_layout_gen.h"),
                   os.path.join(ROOT, "include", "usv_hip.h")]
 
@@ -52,6 +52,7 @@ def build(force: bool = False, verbose: bool = False, probe: bool = False) -> st
 
 def _declare(lib):
     P, I, U64, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_float
+    I64, D = ctypes.c_int64, ctypes.c_double
     sig = {
         "usv_build_lut": [P, P, I, P, P],
         "usv_reset": [P, P, U64, U64, P, P],
@@ -68,6 +69,10 @@ def _declare(lib):
         "usv_eval_mark": [P, P, P, P],
         "usv_eval_step": [P, P, P, P, P],
         "usv_eval_summary": [P, P, P, P, P],
+        "usv_scn_generate": [U64, I64, I, D, D, D, D, D, I, I, P, P, P],
+        "usv_scn_metrics": [P, I, D, D, P, P],
+        "usv_scn_fold": [P, I, I, I, I, D, I, D, I, P, P],
+        "lz_play": [P, P, P, P, P],
         "lz_act": [P, P, P, I, P, P, P, P, P, U64, U64, P, P],
         "lz_value": [P, P, P, P, P],
         "lz_store": [P, P, P, I, P, P, P],

@@ -278,6 +278,32 @@ __global__ __launch_bounds__(TB) void k_lz_forward(lz_cfg_t c, const float *__re
   }
 }
 
+// The deterministic teacher: k_lz_forward<true> without its sampling epilogue.  u = mu + std * 0 is kept as
+// written (the build does not contract or fold it), so the actions carry lz_act's bits for eps_inject = 0.
+__global__ __launch_bounds__(TB) void k_lz_play(lz_cfg_t c, const float *__restrict__ P, const float *__restrict__ obs,
+                                                float *actions_out) {
+  __shared__ NetSmem s;
+  const int n = c.n_envs, D = c.obs_dim;
+  const NetOff o = net_off(D, NA);
+  stage_net(P + actor_base(), o, D, NA, s);
+  const float sd0 = P[std_base(D)], sd1 = P[std_base(D) + 1];
+  const int ntiles = (n + RB - 1) / RB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int row0 = tile * RB, nrows = min(RB, n - row0);
+    stage_rows(obs, row0, nrows, D, s);
+    tile_forward(D, NA, s);
+    const int r = threadIdx.x;
+    if (r < nrows) {
+      const int e = row0 + r;
+      const float mu0 = tanhf(s.out[r * NA]), mu1 = tanhf(s.out[r * NA + 1]);
+      const float u0 = mu0 + sd0 * 0.0f, u1 = mu1 + sd1 * 0.0f;
+      actions_out[2 * e] = tanhf(u0) * c.action_scale[0];
+      actions_out[2 * e + 1] = tanhf(u1) * c.action_scale[1];
+    }
+    __syncthreads();
+  }
+}
+
 __global__ void k_lz_store(lz_cfg_t c, const float *__restrict__ rew, const int64_t *__restrict__ dones, int t,
                            float *st_rew, uint8_t *st_done) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -780,6 +806,14 @@ int lz_act(const lz_cfg_t *cfg, const float *params, const float *obs, int t, fl
   USV_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_lz_forward<false>, dim3(grid), dim3(TB), 0, s, *cfg, params, obs, t, st_obs, st_act, st_logp,
                      st_val, actions_out, (float *)nullptr, seed, step, eps_inject);
+  USV_CHECK_LAUNCH();
+  return 0;
+}
+
+int lz_play(const lz_cfg_t *cfg, const float *params, const float *obs, float *actions_out, void *stream) {
+  if (!cfg_ok(cfg) || !params || !obs || !actions_out) return 1;
+  hipLaunchKernelGGL(k_lz_play, dim3(fwd_grid(cfg->n_envs)), dim3(TB), 0, (hipStream_t)stream, *cfg, params, obs,
+                     actions_out);
   USV_CHECK_LAUNCH();
   return 0;
 }

@@ -173,6 +173,37 @@
   X(USV_EVS_METRICS, "USV_EVS_METRICS") \
   X(USV_EVS_NMETRIC, "USV_EVS_NMETRIC") \
   X(USV_EVS_N, "USV_EVS_N") \
+  X(USV_SCN_SITE_POSE, "USV_SCN_SITE_POSE") \
+  X(USV_SCN_SITE_YAW, "USV_SCN_SITE_YAW") \
+  X(USV_SCN_SITE_OBST, "USV_SCN_SITE_OBST") \
+  X(USV_SCN_MAX_ITERS, "USV_SCN_MAX_ITERS") \
+  X(USV_SCN_MAX_COUNT, "USV_SCN_MAX_COUNT") \
+  X(USV_SCM_D_SPAWN, "USV_SCM_D_SPAWN") \
+  X(USV_SCM_D_GOAL, "USV_SCM_D_GOAL") \
+  X(USV_SCM_D_CORR, "USV_SCM_D_CORR") \
+  X(USV_SCM_D_OO, "USV_SCM_D_OO") \
+  X(USV_SCM_DENSITY, "USV_SCM_DENSITY") \
+  X(USV_SCM_ROWS, "USV_SCM_ROWS") \
+  X(USV_EV_REASON_MIXED, "USV_EV_REASON_MIXED") \
+  X(USV_SCF_PRESENT, "USV_SCF_PRESENT") \
+  X(USV_SCF_SUCCESS_RATE, "USV_SCF_SUCCESS_RATE") \
+  X(USV_SCF_COLL_RATE, "USV_SCF_COLL_RATE") \
+  X(USV_SCF_OOB_RATE, "USV_SCF_OOB_RATE") \
+  X(USV_SCF_COLL_ANY, "USV_SCF_COLL_ANY") \
+  X(USV_SCF_OOB_ANY, "USV_SCF_OOB_ANY") \
+  X(USV_SCF_REASON, "USV_SCF_REASON") \
+  X(USV_SCF_STEPS, "USV_SCF_STEPS") \
+  X(USV_SCF_RETURN, "USV_SCF_RETURN") \
+  X(USV_SCF_FINAL_DIST, "USV_SCF_FINAL_DIST") \
+  X(USV_SCF_MIN_OBS, "USV_SCF_MIN_OBS") \
+  X(USV_SCF_MIN_MARGIN, "USV_SCF_MIN_MARGIN") \
+  X(USV_SCF_VERDICT, "USV_SCF_VERDICT") \
+  X(USV_SCF_DIFFICULTY, "USV_SCF_DIFFICULTY") \
+  X(USV_SCF_ROWS, "USV_SCF_ROWS") \
+  X(USV_SCV_KEEP, "USV_SCV_KEEP") \
+  X(USV_SCV_HARD_REJECT, "USV_SCV_HARD_REJECT") \
+  X(USV_SCV_EASY_REJECT, "USV_SCV_EASY_REJECT") \
+  X(USV_SCV_INCOMPLETE, "USV_SCV_INCOMPLETE") \
   X(PPO_NIN, "PPO_NIN") \
   X(PPO_NH, "PPO_NH") \
   X(PPO_NA, "PPO_NA") \

@@ -5,4 +5,5 @@ storage.RolloutStorage, vecenv.USVRaisimVecEnv)."""
 from .module import Actor, Critic, MLPEncode_wrap, SquashedGaussianDiagonalCovariance  # noqa: F401
 from .ppo import PPO  # noqa: F401
 from .storage import RolloutStorage  # noqa: F401
+from .teacher import LoopzTeacher  # noqa: F401
 from .vecenv import USVRaisimVecEnv  # noqa: F401

@@ -1,0 +1,18 @@
+"""Scenario tables: device mining (sampling), the table format (table), the teacher filter's selection (filter)
+and the playlist runner (runner; needs a GPU, imported on first use)."""
+from .filter import CSV_COLUMNS, eval_rows, select_keep
+from .sampling import (METRIC_KEYS, SamplingParams, build_candidates, metrics_host, philox_host, preselect,
+                       select_from_pre, table_of)
+from .table import load_table, make_table, obstacles_hash, save_table, subset, to_scene_arrays, to_scene_rows
+
+
+def __getattr__(name):
+    if name in ("ScenarioRunner", "fold_to_dict"):
+        from . import runner
+        return getattr(runner, name)
+    raise AttributeError(name)
+
+
+__all__ = ["CSV_COLUMNS", "METRIC_KEYS", "SamplingParams", "ScenarioRunner", "build_candidates", "eval_rows",
+           "fold_to_dict", "load_table", "make_table", "metrics_host", "obstacles_hash", "philox_host", "preselect",
+           "save_table", "select_from_pre", "select_keep", "subset", "table_of", "to_scene_arrays", "to_scene_rows"]

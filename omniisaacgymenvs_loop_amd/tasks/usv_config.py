@@ -50,6 +50,8 @@ _PEN_DEFAULTS = dict(
 )
 
 _NUM = r"([-+]?(?:\d+\.?\d*|\.\d+)(?:[eE][-+]?\d+)?|c1|c2)"
+# CaptureXYTask.collision_threshold as the Python float the reference holds (the kernels compare with its float32)
+COLLISION_THRESHOLD = 1.2
 
 
 def parse_penalty_fn(src: str, consts: Dict[str, float]):
@@ -255,7 +257,7 @@ def build_usv_cfg(task_cfg: Dict[str, Any]) -> UsvCfg:
     c.reward_mode = {"linear": 0, "square": 1, "exponential": 2}[rm]
     c.position_scale, c.exp_coeff = rp["position_scale"], rp["exponential_reward_coeff"]
     c.align_la1, c.align_la2, c.align_la3 = rp["align_la1"], rp["align_la2"], rp["align_la3"]
-    c.collision_threshold = 1.2
+    c.collision_threshold = COLLISION_THRESHOLD
     c.obstacle_radius = 0.5
     c.max_episode_length = int(env["maxEpisodeLength"])
     c.fixed_horizon_eval = int(bool(env.get("fixed_horizon_eval", env.get("fixedHorizonEval", False))))

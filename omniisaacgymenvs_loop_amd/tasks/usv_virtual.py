@@ -193,6 +193,28 @@ class USVVirtual:
         self.scene_next = torch.full((n,), int(sr.get("start_index", 0) or 0), device=self._device, dtype=torch.int32)
         self.scene_last = torch.full((n,), -1, device=self._device, dtype=torch.int32)
 
+    def set_scene_table(self, rows: torch.Tensor, first_row: torch.Tensor) -> None:
+        """Play the scenes of `rows` ([P][USV_SCENE_STRIDE] float32 device tensor, USV_SC_* layout): env e takes
+        row first_row[e] ([n] int32) at its next reset and the following row at every later one, wrapping at P.
+        CaptureXY only; works whether or not env.scene_replay.enabled was set (the reset kernel applies a scene
+        row per env and advances scene_next by one per reset)."""
+        if self.cfg.task_kind != TASK_CAPTURE_XY:
+            raise ValueError("set_scene_table: scenes hold obstacles and a goal position (CaptureXY only)")
+        n, dev = self._num_envs, torch.device(self._device)
+        if (not torch.is_tensor(rows) or rows.dtype != torch.float32 or not rows.is_cuda or rows.dim() != 2
+                or rows.shape[1] != DEFINES["USV_SCENE_STRIDE"] or rows.shape[0] < 1 or not rows.is_contiguous()):
+            raise ValueError(f"rows must be a contiguous float32 [P][{DEFINES['USV_SCENE_STRIDE']}] tensor on {dev}")
+        first = torch.as_tensor(first_row, device=dev)
+        if first.shape != (n,) or first.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"first_row must be [{n}] int32")
+        self._touch()
+        self.scene = rows
+        self.scene_replay_num_scenes = int(rows.shape[0])
+        self.scene_replay_cycle = True
+        self.scene_next = first.to(torch.int32).clone()
+        self.scene_last = torch.full((n,), -1, device=dev, dtype=torch.int32)
+        self._bufs = self._make_bufs()
+
     @property
     def scene_replay_last_scene_idx(self) -> torch.Tensor:
         """Scene index applied at each env's last reset (-1 before the first), on the CPU."""
