@@ -673,6 +673,53 @@ int usv_scn_fold(const usv_eval_t *ev, int n, int S, int R, int K, double collis
                  double easy_margin_min, int max_steps, double *out, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Teacher-vs-student comparison (scripts/rlgames_play_loopz_compare.py:     */
+/* eval.priv_tail_mode :184-522, 1045-1076; scripts/dagger_usv_viz_loopz.py) */
+/* ------------------------------------------------------------------------ */
+
+/* usv_priv_tail modes: what the policy sees in the last cfg->priv_dim columns (the sim is untouched) */
+#define USV_PT_CONST        1   /* base_const_all: the same priv_dim floats (const_tail, device) for every env */
+#define USV_PT_WRONG_RANDOM 2   /* a wrong tail per (env, episode), _compute_wrong_random_tail :296-507 */
+/* Philox site of the wrong tail: ctr = {env, episode[env], 0, USV_PT_SITE}, key = seed; word 0 -> mass, words
+ * 1..3 -> CoM x, y, z; u = w / 2^32 */
+#define USV_PT_SITE 0x50540000
+/* obs_out [n][obs_dim] = obs_in with the last cfg->priv_dim columns replaced (obs_out == obs_in allowed; any other
+ * overlap is not).  One thread per env, no atomics.
+ * WRONG_RANDOM: m = mass_min + (mass_max - mass_min) u0 in double (bounds swapped when reversed); CoM_i = base_com_i
+ * + float32(2 u_i - 1) * com_disp_i (com_mode 1; the base CoM in com_mode 0); mass column m or, mass_relative,
+ * (m - base_mass) / max(|base_mass|, 1e-6) in double, rounded once; CoM columns divided by max(com_scale_i, 1e-6)
+ * when com_scaled (the compare tool's divisor: the env step divides by com_scale_i + 1e-6); r = clip((m -
+ * base_mass) / max(mass_max - base_mass, 1e-6), 0, 1), k_drag = kdrag_min + r (kdrag_max - kdrag_min) when
+ * couple_drag, thr = clip(1 - r thr_rand, 1 - thr_rand, 1) when couple_thr, k_iz likewise, else 1, all in double,
+ * rounded to float32 and encoded as the env step encodes them (raw / centered / minmax).  episode [n] int32 (the
+ * evaluator's ep_count) makes the tail a pure function of (seed, env, episode); NULL = episode 0.
+ * Status 1: NULL argument, n <= 0, unknown mode; status 2: priv_dim not 4 / 8, obs_dim < priv_dim, or WRONG_RANDOM
+ * with the legacy disk CoM (com_mode 2 and com_legacy_r > 0). */
+int usv_priv_tail(const usv_cfg_t *cfg, int mode, const float *obs_in, float *obs_out, int n, int obs_dim,
+                  const float *const_tail, const int32_t *episode, uint64_t seed, void *stream);
+
+/* rows of usv_cmp_fold's output ([USV_CMP_ROWS][S] doubles).  A pair is a playlist row present in both tables. */
+#define USV_CMP_PAIRS         0
+#define USV_CMP_BOTH_SUCC     1   /* reason == goal_tolerance in a and in b */
+#define USV_CMP_ONLY_A        2
+#define USV_CMP_ONLY_B        3
+#define USV_CMP_NEITHER       4
+#define USV_CMP_COLL_A        5   /* pairs that end in a collision in a / in b */
+#define USV_CMP_COLL_B        6
+#define USV_CMP_OOB_A         7
+#define USV_CMP_OOB_B         8
+#define USV_CMP_D_STEPS       9   /* mean len_b - len_a over pairs where both succeed; NaN without one */
+#define USV_CMP_D_RETURN     10   /* means of b - a over all pairs (NaN without a pair) */
+#define USV_CMP_D_FINAL_DIST 11
+#define USV_CMP_D_MIN_MARGIN 12   /* over the pairs whose min_obs_dist_episode is finite in both; NaN without one */
+#define USV_CMP_ROWS         13
+/* the paired per-scenario fold of two evaluator tables of the same playlist (usv_scn_fold's column mapping and
+ * "present" rule, same n, S, R, K).  One thread per scenario, double sums in rollout order: the same tables give
+ * the same bits.  Status as usv_scn_fold; the two tables must keep the same max_episodes (else 2). */
+int usv_cmp_fold(const usv_eval_t *a, const usv_eval_t *b, int n, int S, int R, int K, double collision_threshold,
+                 double *out, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* PPO entry points (rl_games a2c_continuous / a2c_common)                   */
 /* ------------------------------------------------------------------------ */
 
@@ -1042,6 +1089,15 @@ int sysid_encode(const float *enc, int n, int obs_dim, int history_len, int hori
 int sysid_student_step(const float *enc, const float *teacher, int n, int obs_dim, int history_len, int horizon,
                        int base, int s, const float *stream, const int32_t *valid_rows, float *zhat, float *actions,
                        void *stream_);
+/* The deployment student step (forward only): sysid_student_step's arguments, ring geometry, valid_rows semantics
+ * and status codes, plus flags.  SY_PLAY_ZERO_LATENT: zhat = 0 and the encoder is skipped (enc may be NULL), the
+ * ablation of dagger_usv_viz_loopz.py (sysid.zero_latent).  SY_PLAY_SCALAR: the encoder runs on the scalar-FMA
+ * kernel of sysid_student_step (the A/B baseline).  An unknown flag bit is status 1. */
+#define SY_PLAY_ZERO_LATENT 1
+#define SY_PLAY_SCALAR      2
+int sysid_play(const float *enc, const float *teacher, int n, int obs_dim, int history_len, int horizon, int base,
+               int s, int flags, const float *stream, const int32_t *valid_rows, float *zhat, float *actions,
+               void *stream_);
 /* One Adam step on rows [row0, row0 + rows): forward + backward of the encoder, MSE (mean over rows x SY_LAT)
  * against zstar, per-workgroup partial gradients folded in a fixed order into grad [sysid_nparam] by the kernel that
  * applies torch.optim.Adam (betas 0.9 / 0.999, eps 1e-8; adam_step = 1-based step count); *loss_out (device) =

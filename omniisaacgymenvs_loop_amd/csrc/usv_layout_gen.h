@@ -204,6 +204,23 @@
   X(USV_SCV_HARD_REJECT, "USV_SCV_HARD_REJECT") \
   X(USV_SCV_EASY_REJECT, "USV_SCV_EASY_REJECT") \
   X(USV_SCV_INCOMPLETE, "USV_SCV_INCOMPLETE") \
+  X(USV_PT_CONST, "USV_PT_CONST") \
+  X(USV_PT_WRONG_RANDOM, "USV_PT_WRONG_RANDOM") \
+  X(USV_PT_SITE, "USV_PT_SITE") \
+  X(USV_CMP_PAIRS, "USV_CMP_PAIRS") \
+  X(USV_CMP_BOTH_SUCC, "USV_CMP_BOTH_SUCC") \
+  X(USV_CMP_ONLY_A, "USV_CMP_ONLY_A") \
+  X(USV_CMP_ONLY_B, "USV_CMP_ONLY_B") \
+  X(USV_CMP_NEITHER, "USV_CMP_NEITHER") \
+  X(USV_CMP_COLL_A, "USV_CMP_COLL_A") \
+  X(USV_CMP_COLL_B, "USV_CMP_COLL_B") \
+  X(USV_CMP_OOB_A, "USV_CMP_OOB_A") \
+  X(USV_CMP_OOB_B, "USV_CMP_OOB_B") \
+  X(USV_CMP_D_STEPS, "USV_CMP_D_STEPS") \
+  X(USV_CMP_D_RETURN, "USV_CMP_D_RETURN") \
+  X(USV_CMP_D_FINAL_DIST, "USV_CMP_D_FINAL_DIST") \
+  X(USV_CMP_D_MIN_MARGIN, "USV_CMP_D_MIN_MARGIN") \
+  X(USV_CMP_ROWS, "USV_CMP_ROWS") \
   X(PPO_NIN, "PPO_NIN") \
   X(PPO_NH, "PPO_NH") \
   X(PPO_NA, "PPO_NA") \
@@ -245,6 +262,8 @@
   X(SY_MET_SSE, "SY_MET_SSE") \
   X(SY_MET_SST, "SY_MET_SST") \
   X(SY_MET_N, "SY_MET_N") \
+  X(SY_PLAY_ZERO_LATENT, "SY_PLAY_ZERO_LATENT") \
+  X(SY_PLAY_SCALAR, "SY_PLAY_SCALAR") \
   X(ST_TOTAL_REWARD, "ST_TOTAL_REWARD") \
   X(ST_DISTANCE_REWARD, "ST_DISTANCE_REWARD") \
   X(ST_ALIGNMENT_REWARD, "ST_ALIGNMENT_REWARD") \

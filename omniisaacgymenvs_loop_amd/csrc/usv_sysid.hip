@@ -11,6 +11,8 @@
 // stored.  Weight gradients accumulate in registers over every tile of the workgroup (thread (o, cg) owns
 // channels c = 4 cg .. 4 cg + 3 of output channel o) and are written once, as one partial row; k_sy_apply sums
 // the rows in index order (bit-reproducible) and applies Adam.
+//
+// k_sy_play (sysid_play, the deployment step): the same forward on the matrix cores, described where it is defined.
 #include "usv_device.h"
 
 #include <cmath>
@@ -536,6 +538,222 @@ __global__ __launch_bounds__(ATB) void k_sy_action(const float *__restrict__ tea
   }
 }
 
+// ---- k_sy_play: the encoder forward on the matrix cores (sysid_play) ---------------------------------------------
+// One workgroup of 4 waves per tile of RT = 8 windows; every product is a GEMM with N = 32 output channels on
+// v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate): the A operand is the activation (row m = (window, output
+// position), im2col addressing straight from the layer input in LDS), the B operand the weights, kept in LDS as
+// [kidx][32] so that k-step s of lane l reads float 64 s + l (no bank conflict).  kidx = c * K + k (projection: d),
+// and the accumulator starts at the bias: an f32 MFMA is a k-ordered fmaf chain, so every output is the chain
+// k_sy_net's conv_fwd computes.  A wave owns whole 32-row tiles (projection 13 tiles, conv 1 / 2 / 3: 3 / 2 / 1);
+// rows past the last one repeat it and are not written.  LDS: weights 79 KB, the projection of 8 windows 50 KB
+// (rows padded to 1601 floats: the windows of a tile fall on different banks), A1..A3 21 KB.
+namespace play {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int NW = TB / 64;                  // waves
+constexpr int DP = MAXD;                     // k extent of the projection (rows d >= D of W0 are zero)
+constexpr int FS = DP + 1;                   // floats per staged frame (odd: conflict-free A reads)
+constexpr int PROWM = T * C + 1;
+constexpr int MW0 = 0;                       // [DP][32]
+constexpr int MW1 = MW0 + DP * C;            // [C K1][32]
+constexpr int MW2 = MW1 + C * K1 * C;        // [C K2][32]
+constexpr int MW3 = MW2 + C * K2 * C;
+constexpr int MWL = MW3 + C * K2 * C;        // [L][FLAT]
+constexpr int MB = MWL + L * FLAT;           // b0 b1 b2 b3 [32 each], bl [8]
+constexpr int MP = MB + 4 * C + L;
+constexpr int MA1 = MP + RT * PROWM;
+constexpr int MA2 = MA1 + RT * C * L1;
+constexpr int MA3 = MA2 + RT * C * L2;
+constexpr int M_FLOATS = MA3 + RT * C * L3;
+constexpr size_t M_BYTES = (size_t)M_FLOATS * 4;
+constexpr int PTILES = (RT * T + 31) / 32;   // 13
+constexpr int PQ = (PTILES + NW - 1) / NW;   // projection tiles per wave
+constexpr int MAX_PLAY_GROUPS = 256;       // one per CU (the LDS admits one): the weights are staged once
+static_assert(M_BYTES <= 160 * 1024, "k_sy_play LDS");
+static_assert(RT * T * FS <= RT * PROWM, "frames are staged in the projection's space");
+static_assert(DP % 2 == 0 && (C * K1) % 2 == 0 && (C * K2) % 2 == 0, "two k per MFMA");
+static_assert((RT * L1 + 31) / 32 <= NW && (RT * L2 + 31) / 32 <= NW && (RT * L3 + 31) / 32 <= NW, "one tile per wave");
+
+__device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ int acc_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
+
+// one 32-row tile of a conv layer: rows m = (window w, position j) of the RT windows, X [RT][xstride] the layer
+// input ([C][LIN] per window), Y [RT][C LOUT] its output ([C][LOUT] per window), WB [C K][32]
+template <int K, int S, int LIN, int LOUT>
+__device__ __forceinline__ void conv_tile(const float *WB, float bias, const float *X, int xstride, float *Y, int tile,
+                                          int lane) {
+  constexpr int M = RT * LOUT;
+  const int i = lane & 31, h = lane >> 5;
+  const int m = min(tile * 32 + i, M - 1);
+  const int w = m / LOUT, j = m - w * LOUT;
+  const float *xa = X + w * xstride + S * j;
+  const float *wb = WB + lane;
+  f32x16 acc;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) acc[q] = bias;
+  // kidx = 2 s + h = c K + k reads X at c LIN + k.  G k-steps cover a whole number CG of channels, so the offsets
+  // of a group are per-lane constants and its 2 G operand reads do not depend on one another; the next group's
+  // operands are read before this group's products
+  constexpr int G = K % 2 == 0 ? K / 2 : K, CG = 2 * G / K, NG = C / CG;
+  static_assert(C % CG == 0, "whole groups");
+  int offq[G];
+#pragma unroll
+  for (int q = 0; q < G; ++q) offq[q] = ((2 * q + h) / K) * LIN + (2 * q + h) % K;
+  float a[G], b[G], an[G], bn[G];
+#pragma unroll
+  for (int q = 0; q < G; ++q) {
+    a[q] = xa[offq[q]];
+    b[q] = wb[64 * q];
+  }
+#pragma unroll 1
+  for (int gi = 0; gi < NG; ++gi) {
+    const int gn = min(gi + 1, NG - 1);   // the last group re-reads itself
+#pragma unroll
+    for (int q = 0; q < G; ++q) {
+      an[q] = xa[gn * (CG * LIN) + offq[q]];
+      bn[q] = wb[64 * (gn * G + q)];
+    }
+#pragma unroll
+    for (int q = 0; q < G; ++q) acc = mfma(a[q], b[q], acc);
+#pragma unroll
+    for (int q = 0; q < G; ++q) {
+      a[q] = an[q];
+      b[q] = bn[q];
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int mo = tile * 32 + acc_row(q, lane);
+    if (mo < M) {
+      const int wo = mo / LOUT, jo = mo - wo * LOUT;
+      Y[wo * (C * LOUT) + i * LOUT + jo] = leaky(acc[q]);
+    }
+  }
+}
+
+__global__ __launch_bounds__(TB) void k_sy_play(const float *__restrict__ enc, Geo g, int row0, int rows,
+                                                const float *__restrict__ stream,
+                                                const int32_t *__restrict__ valid_rows, float *__restrict__ zhat) {
+  extern __shared__ float lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, o = tid & 31, r = tid >> 5;
+  const int D = g.D;
+  const Off off = offsets(D);
+
+  // weights -> LDS as [kidx][32]
+  for (int i = tid; i < DP * C; i += TB) {
+    const int d = i >> 5, oo = i & 31;
+    lds[MW0 + i] = d < D ? enc[off.w0 + oo * D + d] : 0.f;
+  }
+#pragma unroll 8
+  for (int i = tid; i < C * K1 * C; i += TB) lds[MW1 + i] = enc[off.w1 + (i & 31) * (C * K1) + (i >> 5)];
+#pragma unroll 4
+  for (int i = tid; i < C * K2 * C; i += TB) {
+    lds[MW2 + i] = enc[off.w2 + (i & 31) * (C * K2) + (i >> 5)];
+    lds[MW3 + i] = enc[off.w3 + (i & 31) * (C * K2) + (i >> 5)];
+  }
+  for (int i = tid; i < L * FLAT; i += TB) lds[MWL + i] = enc[off.wl + i];
+  if (tid < C) {
+    lds[MB + tid] = enc[off.b0 + tid];
+    lds[MB + C + tid] = enc[off.b1 + tid];
+    lds[MB + 2 * C + tid] = enc[off.b2 + tid];
+    lds[MB + 3 * C + tid] = enc[off.b3 + tid];
+  }
+  if (tid < L) lds[MB + 4 * C + tid] = enc[off.bl + tid];
+
+  float *F = lds + MP;   // staged frames [RT T][FS], then the projection [RT][PROWM]
+  const int ntiles = (rows + RT - 1) / RT;
+  // thread (r, d = o) owns column d of the T frames of window r.  The frames of the next tile are loaded into
+  // registers before this tile's products and stored to LDS after them: T loads in flight per thread, their
+  // latency under the matrix-core phases
+  float fr[T];
+  auto load_frames = [&](int tile) {
+    const int lr = min(tile * RT + r, rows - 1);   // rows past the end repeat the last one (never written)
+    const int row = row0 + lr, env = row % g.n, s = row / g.n, k0 = T - valid_rows[row];
+    if (o < D) {
+#pragma unroll
+      for (int k = 0; k < T; ++k) fr[k] = stream[((size_t)ring_slot(g, s, max(k, k0)) * g.n + env) * D + o];
+    }
+  };
+#pragma unroll
+  for (int k = 0; k < T; ++k) fr[k] = 0.f;   // columns D <= d < DP stay zero
+  if (blockIdx.x < ntiles) load_frames(blockIdx.x);
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    __syncthreads();   // the previous tile's reads are done (first pass: the weights are in place)
+    if (o < DP) {
+      float *f = F + r * T * FS + o;
+#pragma unroll
+      for (int k = 0; k < T; ++k) f[k * FS] = fr[k];
+    }
+    if (tile + (int)gridDim.x < ntiles) load_frames(tile + gridDim.x);
+    __syncthreads();
+    {  // projection: rows m = w T + t, K = DP
+      f32x16 pacc[PQ];
+      const float b0 = lds[MB + o];
+#pragma unroll
+      for (int q = 0; q < PQ; ++q) {
+        const int tI = wave + NW * q;
+#pragma unroll
+        for (int x = 0; x < 16; ++x) pacc[q][x] = b0;
+        if (tI < PTILES) {
+          const int m = min(tI * 32 + o, RT * T - 1);
+          const float *fa = F + m * FS + (lane >> 5), *wb = lds + MW0 + lane;
+#pragma unroll
+          for (int s = 0; s < DP / 2; ++s) pacc[q] = mfma(fa[2 * s], wb[64 * s], pacc[q]);
+        }
+      }
+      __syncthreads();   // every wave has read its frames
+#pragma unroll
+      for (int q = 0; q < PQ; ++q) {
+        const int tI = wave + NW * q;
+        if (tI < PTILES) {
+#pragma unroll
+          for (int x = 0; x < 16; ++x) {
+            const int m = tI * 32 + acc_row(x, lane);
+            if (m < RT * T) {
+              const int w = m / T, t = m - w * T;
+              lds[MP + w * PROWM + t * C + o] = leaky(pacc[q][x]);
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    if (wave < (RT * L1 + 31) / 32)
+      conv_tile<K1, S1, T, L1>(lds + MW1, lds[MB + C + o], lds + MP, PROWM, lds + MA1, wave, lane);
+    __syncthreads();
+    if (wave < (RT * L2 + 31) / 32)
+      conv_tile<K2, 1, L1, L2>(lds + MW2, lds[MB + 2 * C + o], lds + MA1, C * L1, lds + MA2, wave, lane);
+    __syncthreads();
+    if (wave < (RT * L3 + 31) / 32)
+      conv_tile<K2, 1, L2, L3>(lds + MW3, lds[MB + 3 * C + o], lds + MA2, C * L2, lds + MA3, wave, lane);
+    __syncthreads();
+    const int lrow = tile * RT + r;
+    if (o < L && lrow < rows) {   // linear_output as k_sy_net has it (N = 8: not worth a matrix-core tile)
+      const float *A3 = lds + MA3 + r * C * L3;
+      float acc = lds[MB + 4 * C + o];
+      for (int i = 0; i < FLAT; ++i) acc += lds[MWL + o * FLAT + i] * A3[i];
+      zhat[(size_t)lrow * L + o] = leaky(acc);
+    }
+  }
+}
+
+int launch(const float *enc, const Geo &g, int row0, int rows, const float *stream, const int32_t *valid_rows,
+           float *zhat, hipStream_t s) {
+  if (hipFuncSetAttribute((const void *)k_sy_play, hipFuncAttributeMaxDynamicSharedMemorySize, (int)M_BYTES) !=
+      hipSuccess)
+    return 90;
+  const int nt = (rows + RT - 1) / RT;
+  hipLaunchKernelGGL(k_sy_play, dim3(nt < MAX_PLAY_GROUPS ? nt : MAX_PLAY_GROUPS), dim3(TB), M_BYTES, s, enc, g, row0,
+                     rows, stream, valid_rows, zhat);
+  USV_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace play
+
 // diagnostics in double, two kernels, every sum in a fixed order.  k_sy_moments: block b, thread (q, l) = (tid / 8,
 // tid % 8) sums rows b * 32 + q + 32 gridDim.x i of dimension l: z*, z*^2, z^, z^^2, (z^ - z*)^2; the 32 q's are
 // folded in index order into moments[b][l][5].  k_sy_metrics folds the blocks in index order; the centred sums
@@ -668,6 +886,30 @@ int sysid_student_step(const float *enc, const float *teacher, int n, int obs_di
   if (const int rc = sysid_encode(enc, n, obs_dim, history_len, horizon, base, s * n, n, stream, valid_rows, zhat,
                                   stream_))
     return rc;
+  hipLaunchKernelGGL(k_sy_action, dim3((n + RA - 1) / RA), dim3(ATB), 0, (hipStream_t)stream_, teacher,
+                     geo(n, obs_dim, horizon, base), s, stream, zhat, actions);
+  USV_CHECK_LAUNCH();
+  return 0;
+}
+
+int sysid_play(const float *enc, const float *teacher, int n, int obs_dim, int history_len, int horizon, int base,
+               int s, int flags, const float *stream, const int32_t *valid_rows, float *zhat, float *actions,
+               void *stream_) {
+  if (!teacher || !actions || !stream || !valid_rows || !zhat || s < 0 || s >= horizon) return 1;
+  if (flags & ~(SY_PLAY_ZERO_LATENT | SY_PLAY_SCALAR)) return 1;
+  if (const int rc = check(n, obs_dim, history_len, horizon, base)) return rc;
+  if (flags & SY_PLAY_ZERO_LATENT) {
+    if (hipMemsetAsync(zhat, 0, (size_t)n * L * sizeof(float), (hipStream_t)stream_) != hipSuccess) return 91;
+  } else if (flags & SY_PLAY_SCALAR) {
+    if (const int rc = sysid_encode(enc, n, obs_dim, history_len, horizon, base, s * n, n, stream, valid_rows, zhat,
+                                    stream_))
+      return rc;
+  } else {
+    if (!enc) return 1;
+    if (const int rc = play::launch(enc, geo(n, obs_dim, horizon, base), s * n, n, stream, valid_rows, zhat,
+                                    (hipStream_t)stream_))
+      return rc;
+  }
   hipLaunchKernelGGL(k_sy_action, dim3((n + RA - 1) / RA), dim3(ATB), 0, (hipStream_t)stream_, teacher,
                      geo(n, obs_dim, horizon, base), s, stream, zhat, actions);
   USV_CHECK_LAUNCH();

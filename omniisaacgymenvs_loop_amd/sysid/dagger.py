@@ -22,6 +22,11 @@ from .history import HistoryStream
 from .module import StateHistoryEncoder, action_head_nn
 
 LAT, MET_N = DEFINES["SY_LAT"], DEFINES["SY_MET_N"]
+PLAY_ZERO_LATENT, PLAY_SCALAR = DEFINES["SY_PLAY_ZERO_LATENT"], DEFINES["SY_PLAY_SCALAR"]
+# sysid_play's encoder kernels by name; DEFAULT_PLAY_KERNEL is the one the A/B of profiles/compare_measure.py
+# favours
+PLAY_KERNELS = ("default", "scalar")
+DEFAULT_PLAY_KERNEL = "default"
 
 
 def load_teacher(path: str, obs_dim: int, act_dim: int = 2, *, policy_net=(128, 128), speed_dim: int = 3,
@@ -87,6 +92,15 @@ class USVSysIDAgent:
                    _capi.ptr(hs.stream), _capi.ptr(hs.valid_rows), _capi.ptr(zhat), _capi.ptr(actions),
                    _capi.stream_ptr())
 
+    def play_step(self, hs: HistoryStream, zhat: torch.Tensor, actions: torch.Tensor, zero_latent: bool = False,
+                  scalar: bool = False) -> None:
+        """The deployment step (sysid_play): forward only; zero_latent feeds the action head z^ = 0 and skips the
+        encoder (dagger_usv_viz_loopz.py: sysid.zero_latent), scalar selects the scalar-FMA encoder kernel."""
+        flags = (PLAY_ZERO_LATENT if zero_latent else 0) | (PLAY_SCALAR if scalar else 0)
+        _capi.call("sysid_play", _capi.ptr(self.enc_flat), _capi.ptr(self.teacher_flat), *hs.geometry(), hs.row, flags,
+                   _capi.ptr(hs.stream), _capi.ptr(hs.valid_rows), _capi.ptr(zhat), _capi.ptr(actions),
+                   _capi.stream_ptr())
+
     def encode_rows(self, hs: HistoryStream, row0: int, rows: int, zhat: torch.Tensor) -> None:
         _capi.call("sysid_encode", _capi.ptr(self.enc_flat), *hs.geometry(), int(row0), int(rows), _capi.ptr(hs.stream),
                    _capi.ptr(hs.valid_rows), _capi.ptr(zhat), _capi.stream_ptr())
@@ -96,21 +110,42 @@ class SysIDStudent:
     """The student as a policy: actions = student(obs), obs [n][obs_dim] device tensor (the privileged tail is
     ignored).  It keeps its own history of the observations it was called with, so eval.rollout(task, student,
     evaluator) scores it unchanged.  A policy sees no done flags: the window slides across episode boundaries,
-    as the env wrapper's default mode does; reset() empties it."""
+    as the env wrapper's default mode does; reset() empties it.  zero_latent: the ablation that feeds the action
+    head z^ = 0; kernel: one of PLAY_KERNELS."""
 
-    def __init__(self, agent: USVSysIDAgent, num_envs: int):
+    def __init__(self, agent: USVSysIDAgent, num_envs: int, zero_latent: bool = False,
+                 kernel: str = DEFAULT_PLAY_KERNEL):
+        if kernel not in PLAY_KERNELS:
+            raise ValueError(f"kernel must be one of {PLAY_KERNELS}, got {kernel!r}")
         self.agent = agent
+        self.zero_latent, self.kernel = bool(zero_latent), kernel
         self.history = HistoryStream(num_envs, agent.obs_dim, history_len=agent.history_len, horizon=1,
                                      device=agent.device)
         self.zhat = torch.zeros((num_envs, LAT), device=agent.device)
         self.actions = torch.zeros((num_envs, agent.teacher.output_size), device=agent.device)
+
+    @classmethod
+    def from_files(cls, teacher_pt: str, id_encoder_pth: str, *, num_envs: int, obs_dim: int, history_len: int = 50,
+                   device: str = "cuda:0", zero_latent: bool = False, kernel: str = DEFAULT_PLAY_KERNEL,
+                   **teacher_kw) -> "SysIDStudent":
+        """The student of a loopz `full_<update>.pt` and the `id_encoder_<update>.pth` state dict sysid_distill
+        wrote beside it."""
+        teacher = load_teacher(teacher_pt, obs_dim, **teacher_kw)
+        enc = StateHistoryEncoder(torch.nn.LeakyReLU, input_size=obs_dim - teacher.mass_dim, tsteps=history_len,
+                                  output_size=LAT)
+        sd = torch.load(id_encoder_pth, map_location="cpu", weights_only=True)
+        enc.load_state_dict(sd.get("id_encoder_state_dict", sd) if isinstance(sd, dict) else sd)
+        agent = USVSysIDAgent(teacher=teacher, id_encoder=enc, history_len=history_len,
+                              obs_nonpriv_dim=obs_dim - teacher.mass_dim, device=device)
+        return cls(agent, num_envs, zero_latent=zero_latent, kernel=kernel)
 
     def reset(self) -> None:
         self.history.reset()
 
     def __call__(self, obs: torch.Tensor) -> torch.Tensor:
         self.history.append(torch.nan_to_num(obs.float(), nan=0.0, posinf=0.0, neginf=0.0), None)
-        self.agent.student_step(self.history, self.zhat, self.actions)
+        self.agent.play_step(self.history, self.zhat, self.actions, zero_latent=self.zero_latent,
+                             scalar=self.kernel == "scalar")
         return self.actions
 
 
