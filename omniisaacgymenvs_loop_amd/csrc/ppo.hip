@@ -149,21 +149,9 @@ __device__ __forceinline__ void stage_store_w2(const StagedW &r, MlpSmem &s) {
 
 // tanh(x) = 1 - 2 / (exp(2x) + 1) from one exp2 and one reciprocal (v_exp_f32 / v_rcp_f32) and an fma: |error| <
 // 2e-7 absolute against float64 tanh over the whole range (exp2 overflows to +inf and gives 1, underflows to 0 and
-// gives -1; parity tolerances are 1e-5).  Round 5 used the odd form (1 - e) / (1 + e) of |x| with a 3-term series
-// below 2^-7 for relative accuracy at tiny arguments: ~8 more VALU operations per activation, on the forward's
-// critical path in the gradient and policy kernels, for an accuracy no consumer needs.
-#ifndef USV_TANH_ODD
-#define USV_TANH_ODD 0
-#endif
+// gives -1; parity tolerances are 1e-5).  The odd form (1 - e) / (1 + e) of |x| with a series below 2^-7 was dropped:
+// ~8 more VALU operations per activation on the forward's critical path, for an accuracy no consumer needs.
 __device__ __forceinline__ float fast_tanh(float x) {
-  if constexpr (USV_TANH_ODD != 0) {
-    const float ax = fabsf(x);
-    const float e = __builtin_amdgcn_exp2f(ax * -2.8853900817779268f);   // exp(-2|x|)
-    const float big = (1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e);
-    const float x2 = ax * ax;
-    const float small = ax * (1.0f - x2 * (0.33333334f - 0.13333334f * x2));
-    return copysignf(ax < 0.0078125f ? small : big, x);
-  }
   const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);        // exp(2x)
   return fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
 }
@@ -174,13 +162,9 @@ __device__ __forceinline__ float fast_tanh(float x) {
 // The rollout's experience-buffer stores are non-temporal: the 16 steps' 350 MB at 131072 envs exceed the
 // Infinity Cache and the update reads them only after the rollout, so cached they would only evict the env
 // state the next env step reads (same-box A/B: env step 26.7 -> 24.8 us, rollout and update unchanged)
-#ifndef USV_EXP_NT
-#define USV_EXP_NT 1
-#endif
 template <class T>
 __device__ __forceinline__ void exp_st(T *p, T v) {
-  if constexpr (USV_EXP_NT != 0) __builtin_nontemporal_store(v, p);
-  else *p = v;
+  __builtin_nontemporal_store(v, p);
 }
 constexpr int NUO = (RB * XS + TB - 1) / TB;
 struct ObsCols {
@@ -335,9 +319,6 @@ __device__ __forceinline__ void block_heads(S &s) {
 #define USV_POL_WPC 2
 #endif
 constexpr int POL_WPC = USV_POL_WPC;
-#ifndef USV_POL_L2B
-#define USV_POL_L2B 1   // layer 2 of the register-weight form: a scheduling fence every 16 steps
-#endif
 struct PolSmem {
   float x[RB * XS];       // normalised obs
   float h1[RB * HS];
@@ -411,7 +392,7 @@ __device__ __forceinline__ void block_forward_rw(const RegW &wr, PolSmem &s, Pol
     for (int st = 0; st < NH / 2; ++st) {
       acc = mfma32(s.h1[i * HS + 2 * st + h], wr.w2[st], acc);
       // at most 16 operand reads in flight (a fully hoisted loop would hold 64 of them in registers)
-      if (USV_POL_L2B && st % 16 == 15) __builtin_amdgcn_sched_barrier(0);
+      if (st % 16 == 15) __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) s.h2[crow(r, h) * HS + n0 + i] = fast_tanh(acc[r] + wr.b2);
@@ -1034,20 +1015,10 @@ __global__ __launch_bounds__(RS_TB) void k_obs_rms_seq(ppo_cfg_t c, const double
 // 16 dW2 tiles go two per wave; the row inputs of the losses are loaded with the
 // weights, so nothing in the loss phase waits on memory.
 constexpr int GTB = 512;          // threads per workgroup
-#ifndef USV_BWD_SYNC
-#define USV_BWD_SYNC 0   // 1: dh1 alone on the matrix core, then dW2 beside dz1 -> dW1: measured +1.1 us per minibatch
-                         // (dW2's 64 KB of partial stores then leave in 1.7 us and meet the write bandwidth)
-#endif
-#ifndef USV_BWD_PRIO
-#define USV_BWD_PRIO 0   // s_setprio of the dh1 -> dz1 -> dW1 waves in the two-group backward (1: measured the same)
-#endif
 
 // k_reduce_partials geometry (RED_BLOCKS chunk squares follow the gradient in grad[])
 #ifndef USV_RD_P
 #define USV_RD_P 128
-#endif
-#ifndef USV_RD_NT
-#define USV_RD_NT 1   // non-temporal loads of the partial rows (A/B builds override it)
 #endif
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 constexpr int RD_TB = 512, RD_P = USV_RD_P;            // threads, slots per workgroup
@@ -1199,15 +1170,8 @@ __device__ __forceinline__ int param_of_slot(int s) {
   return -1;
 }
 
-// USV_ROW_NT: the gradient kernel's row inputs (experience rows, read once per mini-epoch) as non-temporal loads
-#ifndef USV_ROW_NT
-#define USV_ROW_NT 0
-#endif
-__device__ __forceinline__ float row_ld(const float *p) {
-  if constexpr (USV_ROW_NT != 0) return __builtin_nontemporal_load(p);
-  else return *p;
-}
-// per-row inputs of the losses (wave 0: lane = row), loaded with the weights
+// per-row inputs of the losses (wave 0: lane = row), loaded with the weights (plain loads: the experience rows
+// are read once per mini-epoch, and non-temporal loads of them measured no gain)
 struct RowIn {
   float act0, act1, nlp, val, ret, adv, mu0, mu1, sg0, sg1;
 };
@@ -1221,7 +1185,7 @@ struct RowIn {
 #define USV_PART_AUX 2   // cache-policy bits of the partial stores: nt (A/B builds override it)
 #endif
 // Partial layout.  Row-major (kCM false; the group fold's): row b = [NPART_PAD] at b NPART_PAD.  Chunk-major
-// (USV_PART_CM, the default otherwise): the reduction's chunks of RD_P slots are the outer index, [chunk][nblk][RD_P],
+// (every other launch): the reduction's chunks of RD_P slots are the outer index, [chunk][nblk][RD_P],
 // so each reduction workgroup reads one contiguous nblk x RD_P block (128 KB at 8192 rows) instead of 256
 // segments 85 KB apart; a gradient workgroup writes its row as RED_BLOCKS segments of 512 B.
 template <int kAux, bool kCM>
@@ -1241,9 +1205,6 @@ struct PartOutT {
     __builtin_amdgcn_raw_buffer_store_b128(v, r, off(idx), 0, kAux);   // idx % 4 == 0: inside one chunk
   }
 };
-#ifndef USV_PART_CM
-#define USV_PART_CM 1
-#endif
 constexpr int AUX_SC1 = 16;   // sc1: write-through (the in-launch group fold reads the rows from another CU)
 
 // ---- The XCD-group fold of the partial rows (kFold launches of k_mb_grad; k_reduce_partials(fold = 1)) ----
@@ -1354,11 +1315,7 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int i = lane & 31, h = lane >> 5;
   const int kh = w >> 2, cb = w & 3, n0 = 32 * cb;      // K half, column block
-#ifdef USV_DIAG_HOT_ROWS
-  const int rb0 = blockIdx.x * RB;   // DIAGNOSTIC build only (wrong rows): every minibatch reads the first one's rows
-#else
   const int rb0 = row0 + blockIdx.x * RB;               // first row of this workgroup
-#endif
   const float invB = 1.0f / (float)c.minibatch;
   USV_PHASE(ppo, 0);
   // several ranks: this minibatch's exchange key (the previous reduction has finished: stream order)
@@ -1398,11 +1355,11 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
   RowIn ri;
   {
     const size_t row = (size_t)rb0 + (lane & (RB - 1));
-    ri.act0 = row_ld(&e_act[row * 2]); ri.act1 = row_ld(&e_act[row * 2 + 1]);
-    ri.nlp = row_ld(&e_nlp[row]); ri.adv = row_ld(&e_adv[row]);
-    ri.val = row_ld(&e_val[row]); ri.ret = row_ld(&e_ret[row]);
-    ri.mu0 = row_ld(&e_mu[row * 2]); ri.mu1 = row_ld(&e_mu[row * 2 + 1]);
-    ri.sg0 = row_ld(&e_sigma[row * 2]); ri.sg1 = row_ld(&e_sigma[row * 2 + 1]);
+    ri.act0 = e_act[row * 2]; ri.act1 = e_act[row * 2 + 1];
+    ri.nlp = e_nlp[row]; ri.adv = e_adv[row];
+    ri.val = e_val[row]; ri.ret = e_ret[row];
+    ri.mu0 = e_mu[row * 2]; ri.mu1 = e_mu[row * 2 + 1];
+    ri.sg0 = e_sigma[row * 2]; ri.sg1 = e_sigma[row * 2 + 1];
   }
   // obs rows and the running statistics (always loaded; obs_rms is non-null, checked on the host)
   constexpr int NU = (RB * XG + GTB - 1) / GTB;
@@ -1411,7 +1368,7 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
     const int q = min(tid + u * GTB, RB * XG - 1), r = q / XG, kc = min(q % XG, NIN - 1);
-    xo[u] = row_ld(&e_obs[(size_t)(rb0 + r) * NIN + kc]);
+    xo[u] = e_obs[(size_t)(rb0 + r) * NIN + kc];
     mu[u] = obs_rms[kc];
     var[u] = obs_rms[NIN + kc];
   }
@@ -1538,7 +1495,7 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
   }
   __syncthreads();
   USV_PHASE(ppo, 12);
-  constexpr bool kCM = USV_PART_CM != 0 && !kFold;
+  constexpr bool kCM = !kFold;
   const PartOutT<kFold ? AUX_SC1 : USV_PART_AUX, kCM> part_st{
       kCM ? __builtin_amdgcn_make_buffer_rsrc(partials + (size_t)blockIdx.x * RD_P, 0,
                                               (int)(((size_t)RED_BLOCKS * gridDim.x - blockIdx.x) * RD_P * 4), 0x00020000)
@@ -1697,10 +1654,9 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
   //   waves 4-7 (row block t of dW2): the head-weight / b2 / bmu / bv sums, then dW2[n in t][k] = sum_r dz2[r][n]
   //     h1[r][k] (4 tiles, each tile's 16-B partial stores spread over the next tile's chain).
   // The two groups share each SIMD's matrix core, so dW2's 64 KB of partial stores leave over the whole backward
-  // (USV_BWD_SYNC = 1 runs dh1 alone first and measured slower: the stores then meet the write bandwidth) ----
+  // (a barrier that runs dh1 alone first measured +1.1 us per minibatch: the stores then meet the write bandwidth) ----
   f32x16 dh = {};
   if (w < 4) {
-    if constexpr (USV_BWD_PRIO > 0) __builtin_amdgcn_s_setprio(USV_BWD_PRIO);
     if constexpr (kBf) {
 #pragma unroll
       for (int st = 0; st < NH / 16; ++st) {
@@ -1730,7 +1686,6 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
       part_st(tail_slot(q < 2 ? PPO_OFF_BMU + q : PPO_OFF_BV), sacc);
     }
   }
-  if constexpr (USV_BWD_SYNC != 0) __syncthreads();
   if (w < 4) {
     float dz1[16];
 #pragma unroll
@@ -2080,14 +2035,9 @@ __global__ __launch_bounds__(RD_TB) void k_reduce_partials(const float *__restri
 #pragma unroll
     for (int k = 0; k < RD_KB; ++k) {
       const int row = min(b0 + RD_G * k, nblk - 1);
-      const float4 *src = USV_PART_CM ? P4 + ((size_t)blockIdx.x * nblk + row) * RD_L + col
-                                      : P4 + (size_t)row * (NPART_PAD / 4) + p4c;
-#if USV_RD_NT
+      const float4 *src = P4 + ((size_t)blockIdx.x * nblk + row) * RD_L + col;   // chunk-major (PartOutT)
       const f32x4v v = __builtin_nontemporal_load(reinterpret_cast<const f32x4v *>(src));   // read once
       x[k] = make_float4(v[0], v[1], v[2], v[3]);
-#else
-      x[k] = *src;
-#endif
     }
     // the bias corrections in the shadow of the row loads (they wait on opt_in only)
 #pragma unroll

@@ -91,12 +91,6 @@ struct ResetRng {
 // Per-step scratch reset (reset count, field maxima, extras sums): one tiny
 // kernel instead of four memset nodes.
 // ------------------------------------------------------------------------
-// USV_RESET_FOLD_KERNEL: the episode-extras fold of the reset path in a one-workgroup launch of its own
-// (k_extras_fold) instead of by the last k_reset workgroup behind a device-scope counter and fences
-#ifndef USV_RESET_FOLD_KERNEL
-#define USV_RESET_FOLD_KERNEL 1
-#endif
-
 __global__ void k_step_begin(usv_bufs_t b, double step_inc) {
   const int t = threadIdx.x;
   if (t == 0 && b.clock) {   // device step clock: this step's index and bias-call count
@@ -416,7 +410,8 @@ __global__ __launch_bounds__(kBlock) void k_reset(usv_cfg_t c, usv_bufs_t b, uin
     b.ctl[USV_CTL_H_INJ_HI] = (int32_t)(uint32_t)((uint64_t)(uintptr_t)inj >> 32);
     b.ctl[USV_CTL_PLACE] = b.scene ? 0 : 1;   // scene replay: obstacles come from the scene
   }
-  // ---- the last workgroup finalises extras["episode"] = means over this step's resets (:1591-1612).
+  // ---- extras["episode"] = means over this step's resets (:1591-1612), finalised by k_extras_fold in a
+  // one-workgroup launch of its own (no device-scope completion counter and fences in this kernel).
   // Per-workgroup partials (no float atomics: one address per statistic would serialise
   // every wave of the grid on it, and the sum order would vary run to run) ----
   __syncthreads();
@@ -426,11 +421,7 @@ __global__ __launch_bounds__(kBlock) void k_reset(usv_cfg_t c, usv_bufs_t b, uin
 #pragma unroll
     for (int w = 1; w < kBlock / 64; ++w) a += wsum[w][qs];
     b.extras_acc[(size_t)blockIdx.x * USV_NSTAT + qs] = a;
-#if !USV_RESET_FOLD_KERNEL
-    __threadfence();
-#endif
   }
-#if USV_RESET_FOLD_KERNEL
   // the fold runs as k_extras_fold right behind this launch (stream order publishes the partials)
 }
 
@@ -439,20 +430,6 @@ __global__ __launch_bounds__(kBlock) void k_extras_fold(usv_cfg_t c, usv_bufs_t 
   __shared__ float fold[8][32];
   const int count = min(b.ctl[USV_CTL_RESET_COUNT], b.n);
   const int G = nblk;
-#else
-  __shared__ bool last;
-  __shared__ float fold[8][32];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    last = atomicAdd(&b.ctl[USV_CTL_OBST_DONE], 1) == (int)gridDim.x - 1;
-    __threadfence();
-  }
-  __syncthreads();
-  if (!last) return;
-  const int count = b.ctl[USV_CTL_RESET_COUNT];
-  const int G = (int)gridDim.x;
-#endif
   if (c.stats_on && count > 0) {
     // 8 interleaved block subsets per statistic, each summed in block order, then combined in order
     static_assert(USV_NSTAT <= 32 && kBlock == 256, "fold layout");
@@ -1913,12 +1890,10 @@ int usv_reset_part(const usv_cfg_t *cfg, const usv_bufs_t *b, uint64_t seed, uin
     hipLaunchKernelGGL(k_reset, dim3(grid), dim3(kBlock), 0, s, *cfg, *b, seed, step, u_inject);
     USV_CHECK_LAUNCH();
   }
-#if USV_RESET_FOLD_KERNEL
   if (part != 1 && cfg->stats_on) {
     hipLaunchKernelGGL(k_extras_fold, dim3(1), dim3(kBlock), 0, s, *cfg, *b, grid);
     USV_CHECK_LAUNCH();
   }
-#endif
   return 0;
 }
 

@@ -155,24 +155,11 @@ __global__ __launch_bounds__(kPlaceTB) void k_field_place(usv_cfg_t c, usv_bufs_
 // SIMD -- for batches that fill the chip more than once; k_field_wave keeps the
 // compiler's 256 + 76 registers and one env per CU, for small batches, where the
 // kernel is latency-bound and a shared CU would only slow the slowest env.
-// USV_SWEEP_CHG 1: a sweep notes a lowered cell by OR-ing the old ^ new bit patterns into a per-lane VGPR
-// (updates only ever lower a value, so the tile changed iff the OR is non-zero); 0: a per-cell compare into a
-// lane mask (one VALU compare + one SALU OR per cell, the SALU op waiting on the compare)
-// 2: the same OR as ONE v_bitop3_b32 per cell (chg | (old ^ new), truth table 0xF6 over the operand constants
+// A sweep notes a lowered cell by OR-ing the old ^ new bit patterns into a per-lane VGPR (updates only ever lower
+// a value, so the tile changed iff the OR is non-zero; no per-cell compare into a lane mask, whose SALU OR waits on
+// the compare), as ONE v_bitop3_b32 per cell (chg | (old ^ new), truth table 0xF6 over the operand constants
 // 0xF0 / 0xCC / 0xAA) where the compiler emits an XOR per cell plus an OR3 per two cells
-#ifndef USV_SWEEP_CHG
-#define USV_SWEEP_CHG 2
-#endif
-#ifndef USV_SWEEP_FNOTE_EDGE
-#define USV_SWEEP_FNOTE_EDGE 1
-#endif
-#if USV_SWEEP_CHG == 2
 #define USV_SWEEP_NOTE(hb, m) (chg = __builtin_amdgcn_bitop3_b32(chg, (uint32_t)(hb), (uint32_t)(m), 0xF6))
-#elif USV_SWEEP_CHG
-#define USV_SWEEP_NOTE(hb, m) (chg |= (uint32_t)((hb) ^ (m)))
-#else
-#define USV_SWEEP_NOTE(hb, m) (changed |= (m) < (hb))
-#endif
 // TH x TW tiles (10 x 10: the packed and plain kernels; 10 x 5: the small-batch kernel, two waves per SIMD for one
 // env) over NTHR threads; the field buffer keeps its 10 x 10 tiles (a 10 x 5 tile stores into half of one)
 template <bool kPlace, int TH = T, int TW = T, int NTHR = kWaveThreads>
@@ -331,9 +318,7 @@ __device__ __forceinline__ void field_wave_body(const usv_cfg_t &c, const usv_bu
     int it = 0;
     for (; it < kMaxIters; ++it) {
       int changed = 0;
-#if USV_SWEEP_CHG
       uint32_t chg = 0u;   // OR of (old ^ new) over the tile's cells: a VGPR, no per-cell lane-mask SALU op
-#endif
       bool dirty = false;
       if (tile_ok) {
 #pragma unroll
@@ -374,12 +359,12 @@ __device__ __forceinline__ void field_wave_body(const usv_cfg_t &c, const usv_bu
             m = min(m, __float_as_int(fabsf(h[i - 1][j]) + 1.0f));
             m = min(m, __float_as_int(fabsf(h[i - 1][j + 1]) + 1.414f));
             m = min(m, __float_as_int(fabsf(h[i][j - 1]) + 1.0f));
-            // USV_SWEEP_FNOTE_EDGE: the forward pass notes only the tile's edge cells (the halos its neighbours
+            // The forward pass notes only the tile's edge cells (the halos its neighbours
             // read).  The backward pass notes every cell, and a backward pass that lowers nothing leaves the tile
             // at its fixed point under the current halos (after the forward pass every forward constraint holds;
             // the unchanged backward pass keeps them and adds the backward ones), so an interior cell lowered by
             // the forward pass alone needs no further sweep of this tile or of its neighbours
-            if (USV_SWEEP_FNOTE_EDGE == 0 || i == 1 || i == TH || j == 1 || j == TW) USV_SWEEP_NOTE(hb, m);
+            if (i == 1 || i == TH || j == 1 || j == TW) USV_SWEEP_NOTE(hb, m);
             h[i][j] = __int_as_float(m);
           }
 #pragma unroll
@@ -396,11 +381,9 @@ __device__ __forceinline__ void field_wave_body(const usv_cfg_t &c, const usv_bu
             USV_SWEEP_NOTE(hb, m);
             h[i][j] = __int_as_float(m);
           }
-#if USV_SWEEP_CHG
         // opaque to the optimiser: otherwise it folds (OR of old ^ new) != 0 back into per-cell compares
         __asm__("" : "+v"(chg));
         changed = chg != 0u;
-#endif
         if (changed) {
 #pragma unroll
           for (int k = 0; k < TW; ++k) {
@@ -511,15 +494,8 @@ __device__ __forceinline__ BatchK batch_k(const usv_cfg_t &c, const usv_bufs_t &
 // (19 column pairs x 3 row groups), so the obstacles that can reach it are few (a per-wave mask)
 // and many of its row strips lie out of every obstacle's reach, where the SDF cannot enter the
 // statistics and a cell contributes only through its cost (the "far" path below).
-// USV_STATS_PIPE=1: k_field_stats loads the next item's costs during the current one (0: at the item's start)
-#ifndef USV_STATS_PIPE
-#define USV_STATS_PIPE 0
-#endif
-// USV_STATS_REG_OBST=1: every obstacle's (gx - ox)^2 and oy in registers across the band (0: the mask's from LDS,
-// 48 fewer VGPRs: with USV_STATS_WAVES 5 waves per SIMD instead of 4, -5% on the kernel late in training)
-#ifndef USV_STATS_REG_OBST
-#define USV_STATS_REG_OBST 0
-#endif
+// The obstacles a wave's block needs come from LDS through its mask, not from 48 registers held across the band:
+// with USV_STATS_WAVES 5 waves per SIMD instead of 4, -5% on the kernel late in training.
 // USV_STATS_WAVES: k_field_stats' minimum waves per SIMD (its register budget: 5 -> 96 VGPRs, no spills with the LDS
 // obstacles; 6 spills)
 #ifndef USV_STATS_WAVES
@@ -564,51 +540,16 @@ __global__ __launch_bounds__(256, USV_STATS_WAVES) void k_field_stats(usv_cfg_t 
       dst[k] = *reinterpret_cast<const float2 *>(F + field_idx(r, c0));
     }
   };
-  // USV_STATS_PIPE: a software pipeline over the workgroup's items -- the next item's obstacle coordinates and slot
-  // index load at the top of an item, its costs after the current SDF, so they arrive during this item's statistics
-  float2 gA[kBandIters], gB[kBandIters];
-  float so_nx = 0.f;
-#if USV_STATS_PIPE
-  if ((int)blockIdx.x < items) {
-    const int sl = (int)blockIdx.x / kBands;
-    load_costs((int)blockIdx.x, b.reset_ids[sl], gA);
-    if (tid < 2 * USV_NOBST) so_nx = b.slot_stats[(size_t)sl * kSlotStride + kSlotObst + tid];
-  }
-#endif
-  // one item: the statistics of band w % kBands of slot w / kBands from the costs in gv (pipelined: loaded by
-  // the previous item) while the next item's costs load into gnx
-  const auto item = [&](const int w, float2 (&gv)[kBandIters], float2 (&gnx)[kBandIters]) {
+  // one item: the statistics of band w % kBands of slot w / kBands, from the costs loaded into gv at its start
+  // (gv lives outside the item: as a local of it the kernel compiles to other code)
+  float2 gA[kBandIters];
+  const auto item = [&](const int w, float2 (&gv)[kBandIters]) {
     const int slot = w / kBands, band = w % kBands;
-#if USV_STATS_PIPE
-    if (tid < 2 * USV_NOBST) so[tid] = so_nx;
-    if (tid < 2) flags[tid] = 0;
-    __syncthreads();
-    // the next item (this one again after the last: loads without a branch, so the wait counts stay exact)
-    const int wn = w + (int)gridDim.x < items ? w + (int)gridDim.x : w;
-    const int en = b.reset_ids[wn / kBands];
-    if (tid < 2 * USV_NOBST) so_nx = b.slot_stats[(size_t)(wn / kBands) * kSlotStride + kSlotObst + tid];
-#else
     if (tid < 2 * USV_NOBST) so[tid] = b.slot_stats[(size_t)slot * kSlotStride + kSlotObst + tid];
     if (tid < 2) flags[tid] = 0;
     __syncthreads();
     load_costs(w, b.reset_ids[slot], gv);
-#endif
-#if USV_STATS_REG_OBST
-    float dxa[USV_NOBST], dxb[USV_NOBST], oy[USV_NOBST];
-    {
-      const float gxa = slin[c0], gxb = slin[c0 + 1];
-#pragma unroll
-      for (int o = 0; o < USV_NOBST; ++o) {
-        const float ox = so[2 * o];
-        const float da = gxa - ox, db = gxb - ox;
-        dxa[o] = da * da;
-        dxb[o] = db * db;
-        oy[o] = so[2 * o + 1];
-      }
-    }
-#else
     const float gxa = slin[c0], gxb = slin[c0 + 1];
-#endif
     // Obstacles that can matter to this wave's block: the SDF enters the statistics only through j_raw (0
     // unless dist - 2 r_obs < influence_radius) and the inside test (dist <= 2 r_obs), so an obstacle farther
     // than far_d from the whole block (in x or in y) can only be the minimum of a cell whose SDF is irrelevant
@@ -668,18 +609,6 @@ __global__ __launch_bounds__(256, USV_STATS_WAVES) void k_field_stats(usv_cfg_t 
       gy[k] = slin[band * kBandRows + rgc + kRowGroups * k];
       a[k] = bb[k] = 0x7F800000u;
     }
-#if USV_STATS_REG_OBST
-#pragma unroll
-    for (int o = 0; o < USV_NOBST; ++o) {
-      if (!((omask >> o) & 1u)) continue;   // uniform
-#pragma unroll
-      for (int k = 0; k < kBandIters; ++k) {
-        const float dy = gy[k] - oy[o];
-        a[k] = min(a[k], __float_as_uint(fmaf(dy, dy, dxa[o])));
-        bb[k] = min(bb[k], __float_as_uint(fmaf(dy, dy, dxb[o])));
-      }
-    }
-#else
     // the mask's obstacles only (a scalar loop over its set bits; the coordinates are LDS broadcasts): no
     // per-obstacle registers
     for (uint32_t om = omask; om != 0u; om &= om - 1u) {
@@ -694,10 +623,6 @@ __global__ __launch_bounds__(256, USV_STATS_WAVES) void k_field_stats(usv_cfg_t 
         bb[k] = min(bb[k], __float_as_uint(fmaf(dy, dy, dxb)));
       }
     }
-#endif
-#if USV_STATS_PIPE
-    load_costs(wn, en, gnx);
-#endif
 #pragma unroll
     for (int k = 0; k < kBandIters; ++k) {
       // a row strip of the block whose cells all lie out of reach takes the far path (uniform branch)
@@ -740,18 +665,7 @@ __global__ __launch_bounds__(256, USV_STATS_WAVES) void k_field_stats(usv_cfg_t 
     }
     __syncthreads();
   };
-#if USV_STATS_PIPE
-  // the two cost buffers in turn: no register copies between items (a copy would wait for the loads)
-  for (int w = blockIdx.x; w < items;) {
-    item(w, gA, gB);
-    w += (int)gridDim.x;
-    if (w >= items) break;
-    item(w, gB, gA);
-    w += (int)gridDim.x;
-  }
-#else
-  for (int w = blockIdx.x; w < items; w += gridDim.x) item(w, gA, gB);
-#endif
+  for (int w = blockIdx.x; w < items; w += gridDim.x) item(w, gA);
 }
 
 // ------------------------------------------------------------- pass C2 ---
@@ -906,15 +820,9 @@ namespace {
 // stage 1: the obstacle placement alone (k_field_place); stage 2: the rest after it (sweeps, exactness
 // fallback, statistics, batch fold, constants) = stage 3 (sweeps, fallback, statistics) + stage 4 (batch fold,
 // constants)
-// k_field_stats' grid: workgroups loop over (slot, band) items; USV_STATS_GRID caps it (default 4096)
-static int stats_grid(int n) {
-  static const int cap = [] {
-    const char *v = getenv("USV_STATS_GRID");
-    const int x = v ? atoi(v) : 0;
-    return x > 0 ? x : 4096;
-  }();
-  return n * kBands < cap ? n * kBands : cap;
-}
+// k_field_stats' grid: workgroups loop over (slot, band) items, at most kStatsGridCap of them
+constexpr int kStatsGridCap = 4096;
+static int stats_grid(int n) { return n * kBands < kStatsGridCap ? n * kBands : kStatsGridCap; }
 
 int field_stages(const usv_cfg_t *cfg, const usv_bufs_t *b, int stage, hipStream_t s) {
   const int grid_b = b->n < 512 ? b->n : 512;

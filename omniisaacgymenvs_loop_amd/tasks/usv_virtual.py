@@ -158,7 +158,6 @@ class USVVirtual:
         # stream for the field kernels and the fork / join events
         self.rstash = Z((DEFINES["USV_RSTASH_ROWS"], n), **f32) if self._has_field else None
         self._side = None
-        self._ev_stats = None
         self._step_pending = False
         self._late_pending = False   # USV_LATE_ON_JOIN: an overlapped step's deferred reward waits for join_step
         self._host_dirty = True   # host-side buffer writes since the last join (the allocation's fills)
@@ -455,28 +454,9 @@ class USVVirtual:
         cfg, b = _capi.byref(self.cfg), _capi.byref(self._bufs)
         main = torch.cuda.current_stream(self._device)
         if self._side is None:
-            # USV_SIDE_PRIORITY: the side stream's priority (torch's convention: lower = higher priority)
-            self._side = torch.cuda.Stream(device=self._device, priority=int(os.getenv("USV_SIDE_PRIORITY", "0")))
+            self._side = torch.cuda.Stream(device=self._device)
             self._ev_fork, self._ev_early, self._ev_join = (torch.cuda.Event() for _ in range(3))
         side = self._side
-        # USV_STATS_FIRST=1: the main stream (the next policy step) waits for the field statistics, which then
-        # run alone instead of beside the policy kernel (A/B knob)
-        stats_first = os.getenv("USV_STATS_FIRST", "0") == "1"
-
-        def side_fields():
-            if stats_first:
-                if self._ev_stats is None:
-                    self._ev_stats = torch.cuda.Event()
-                _capi.call("usv_field_stage", cfg, b, 3, side.cuda_stream)
-                self._ev_stats.record(side)
-                _capi.call("usv_field_stage", cfg, b, 4, side.cuda_stream)
-            else:
-                _capi.call("usv_field_stage", cfg, b, 2, side.cuda_stream)
-
-        # USV_SIDE_FIRST=1 (default): the side stream's field kernels are captured right after the fork, before this
-        # stream's deferred store and extras fold (a captured graph's launch gives the placement's first dependent
-        # its queue, so the sweeps then follow the placement on one queue); 0: after them
-        side_first = os.getenv("USV_SIDE_FIRST", "1") == "1" and not reset_on_side
         if reset_on_side:
             # reset + obstacle placement on the side stream behind the previous step's deferred reward; this
             # stream waits for the placement, then folds the episode extras (so what it reads of them between
@@ -486,22 +466,21 @@ class USVVirtual:
             self._ev_fork.record(side)
             main.wait_event(self._ev_fork)
             _capi.call("usv_reset_part", cfg, b, self.seed, k, None, 2, main.cuda_stream)
+            _capi.call("usv_field_stage", cfg, b, 2, side.cuda_stream)
         else:
             _capi.call("usv_field_stage", cfg, b, 1, main.cuda_stream)
             self._ev_fork.record(main)
             side.wait_event(self._ev_fork)
-            if side_first:
-                side_fields()
+            # the side stream's field kernels are captured right after the fork, before this stream's deferred
+            # store and extras fold (a captured graph's launch gives the placement's first dependent its queue,
+            # so the sweeps then follow the placement on one queue)
+            _capi.call("usv_field_stage", cfg, b, 2, side.cuda_stream)
             if after_fork is not None:
                 after_fork()
             if fold_late:
                 _capi.call("usv_reset_part", cfg, b, self.seed, k, None, 2, main.cuda_stream)
-        if not side_first:
-            side_fields()
         _capi.call("usv_env_step_part", cfg, b, _capi.ptr(actions), _capi.ptr(self.lut), ctypes.c_float(bias),
                    self.seed, k, _capi.ptr(u_step), 3, main.cuda_stream)
-        if stats_first:
-            main.wait_event(self._ev_stats)
         # USV_LATE_ON_JOIN=1: the deferred reward runs on the joining stream right after its wait for the fields; 0: on
         # the side stream behind part 3.  Unset: 0 from 32768 envs (the packed-sweep batches: with the round-6
         # schedule the side queue then runs constants -> deferred reward -> next reset back to back, rollout -1.6% at
