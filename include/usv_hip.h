@@ -720,6 +720,60 @@ int usv_cmp_fold(const usv_eval_t *a, const usv_eval_t *b, int n, int S, int R, 
                  double *out, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Analysis of a comparison (analyze_play_csv.py: the paired Layer-0        */
+/* :597-700, Layer-0 :464-594, the stratified effect curves :883-985)        */
+/* ------------------------------------------------------------------------ */
+
+/* rows of usv_ana_pair_deltas' output ([USV_ANA_PD_ROWS][S] doubles), the reference's metrics in its order */
+#define USV_ANA_PD_SUCCESS      0   /* success_rate */
+#define USV_ANA_PD_COLLISION    1   /* collision_rate */
+#define USV_ANA_PD_OOB          2   /* out_of_bounds_rate */
+#define USV_ANA_PD_RET_SCALED   3   /* return_scaled_mean: USV_EV_RETURN x reward_scale */
+#define USV_ANA_PD_RET_RAW      4   /* return_raw_mean */
+#define USV_ANA_PD_PATH_EFF     5   /* path_efficiency_mean */
+#define USV_ANA_PD_PATH_LEN     6   /* path_length_mean */
+#define USV_ANA_PD_TIME_SUCC    7   /* time_to_goal_sec_success_mean: over the side's successes */
+#define USV_ANA_PD_STEPS_SUCC   8   /* steps_to_goal_mean_success: USV_EV_LEN_STEPS over the side's successes */
+#define USV_ANA_PD_MIN_OBS_SUCC 9   /* min_obs_dist_min_success_mean: USV_EV_MIN_OBS_EP over the side's successes */
+#define USV_ANA_PD_ROWS        10
+/* row m of scenario s = nanmean(metric_m | treat, s) - nanmean(metric_m | control, s) over each side's present
+ * rollouts (_paired_deltas :633-650; the success-only rows over that side's rollouts with USV_EV_SUCCESS == 1), NaN
+ * when a side has no such rollout or a mean that is not finite.  usv_scn_fold's column mapping and "present" rule,
+ * one thread per scenario, double sums in rollout order: the same tables give the same bits.  Status as
+ * usv_cmp_fold. */
+int usv_ana_pair_deltas(const usv_eval_t *control, const usv_eval_t *treat, int n, int S, int R, int K,
+                        double reward_scale, double *out, void *stream);
+
+#define USV_ANA_MAX_BOOT 4096        /* largest B (replicates) per call */
+#define USV_ANA_MAX_Q       8        /* largest nq per call */
+#define USV_ANA_LDS_DOUBLES 16384    /* a segment up to this length is staged in LDS, a longer one is gathered from
+                                        global memory */
+/* Philox site of the bootstrap: draw i of replicate b of segment j is word i & 3 of ctr = {i >> 2, b, j,
+ * USV_ANA_SITE}, key = seed; idx = (uint64(word) * len) >> 32 */
+#define USV_ANA_SITE 0x414E0000
+/* The segmented bootstrap of the mean.  Segment j is values[seg_off[j] .. seg_off[j + 1]) (len elements); means[j][b]
+ * = the nanmean of len draws with replacement from it (sum and count of the draws that are not NaN; NaN when the
+ * count is 0, len = 0 included; infinities propagate).  values, inj_idx, idx_out and means are device arrays; seg_off
+ * and inj_off [J + 1] are HOST arrays (read before the launch: the limits below are checked on them).
+ * inj_idx != NULL: draw i of (j, b) is inj_idx[inj_off[j] + b len + i] instead of the Philox index (a value outside
+ * [0, len) counts as a NaN draw).  idx_out != NULL: the indices used are also written there, in the same layout.
+ * One wave per replicate, every lane sums its own draws in index order and the lanes are folded in a fixed tree, no
+ * atomics: the same inputs and seed give the same bits.
+ * Status 1: a NULL argument, J < 1, B < 1, offsets that decrease, inj_idx or idx_out without inj_off, or an
+ * inj_off[j + 1] - inj_off[j] below B len; status 2: a len past USV_SCN_MAX_COUNT, B past USV_ANA_MAX_BOOT. */
+int usv_ana_bootstrap(const double *values, const int64_t *seg_off, int J, int B, uint64_t seed,
+                      const int32_t *inj_idx, const int64_t *inj_off, int32_t *idx_out, double *means, void *stream);
+
+#define USV_ANA_NAN_PROPAGATE 0   /* np.quantile: a NaN in the row makes every output NaN */
+#define USV_ANA_NAN_IGNORE    1   /* np.nanquantile: over the values that are not NaN; NaN without one */
+/* out[j][k] = numpy's default ("linear") quantile q[k] of row j of x [J][B]: the m values sorted, pos = q (m - 1),
+ * lo = floor(pos), g = pos - lo, a = v[lo], b = v[min(lo + 1, m - 1)]; a + (b - a) g when g < 0.5, else
+ * b - (b - a)(1 - g) (numpy's _lerp).  One workgroup per row, sorted in LDS.  x, q (nq doubles in [0, 1]) and out are
+ * device arrays.  Status 1: a NULL argument, J < 1, B < 1, nq < 1, unknown nan_mode; status 2: B past
+ * USV_ANA_MAX_BOOT, nq past USV_ANA_MAX_Q. */
+int usv_ana_quantiles(const double *x, int J, int B, const double *q, int nq, int nan_mode, double *out, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* PPO entry points (rl_games a2c_continuous / a2c_common)                   */
 /* ------------------------------------------------------------------------ */
 

@@ -22,7 +22,8 @@ LIB_PATH = os.path.join(LIB_DIR, "libusv_hip.so")
 # instrumented build (per-workgroup phase timestamps, tools/phase_probe.py); selected with USV_HIP_PROBE=1
 PROBE_LIB_PATH = os.path.join(LIB_DIR, "libusv_hip_probe.so")
 SOURCES = [os.path.join(HERE, "csrc", f) for f in ("usv_env.hip", "usv_field.hip", "usv_eval.hip", "ppo.hip", "loopz.hip",
-                                                    "usv_sysid.hip", "usv_scenario.hip", "usv_compare.hip")]
+                                                    "usv_sysid.hip", "usv_scenario.hip", "usv_compare.hip",
+                                                    "usv_analysis.hip")]
 DEPS = SOURCES + [os.path.join(HERE, "csrc", "usv_device.h"), os.path.join(HERE, "csrc", "usv_layout_gen.h"),
                   os.path.join(ROOT, "include", "usv_hip.h")]
 
@@ -74,6 +75,9 @@ def _declare(lib):
         "usv_scn_fold": [P, I, I, I, I, D, I, D, I, P, P],
         "usv_priv_tail": [P, I, P, P, I, I, P, P, U64, P],
         "usv_cmp_fold": [P, P, I, I, I, I, D, P, P],
+        "usv_ana_pair_deltas": [P, P, I, I, I, I, D, P, P],
+        "usv_ana_bootstrap": [P, P, I, I, U64, P, P, P, P, P],
+        "usv_ana_quantiles": [P, I, I, P, I, I, P, P],
         "lz_play": [P, P, P, P, P],
         "lz_act": [P, P, P, I, P, P, P, P, P, U64, U64, P, P],
         "lz_value": [P, P, P, P, P],

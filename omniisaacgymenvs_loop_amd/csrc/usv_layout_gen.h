@@ -221,6 +221,23 @@
   X(USV_CMP_D_FINAL_DIST, "USV_CMP_D_FINAL_DIST") \
   X(USV_CMP_D_MIN_MARGIN, "USV_CMP_D_MIN_MARGIN") \
   X(USV_CMP_ROWS, "USV_CMP_ROWS") \
+  X(USV_ANA_PD_SUCCESS, "USV_ANA_PD_SUCCESS") \
+  X(USV_ANA_PD_COLLISION, "USV_ANA_PD_COLLISION") \
+  X(USV_ANA_PD_OOB, "USV_ANA_PD_OOB") \
+  X(USV_ANA_PD_RET_SCALED, "USV_ANA_PD_RET_SCALED") \
+  X(USV_ANA_PD_RET_RAW, "USV_ANA_PD_RET_RAW") \
+  X(USV_ANA_PD_PATH_EFF, "USV_ANA_PD_PATH_EFF") \
+  X(USV_ANA_PD_PATH_LEN, "USV_ANA_PD_PATH_LEN") \
+  X(USV_ANA_PD_TIME_SUCC, "USV_ANA_PD_TIME_SUCC") \
+  X(USV_ANA_PD_STEPS_SUCC, "USV_ANA_PD_STEPS_SUCC") \
+  X(USV_ANA_PD_MIN_OBS_SUCC, "USV_ANA_PD_MIN_OBS_SUCC") \
+  X(USV_ANA_PD_ROWS, "USV_ANA_PD_ROWS") \
+  X(USV_ANA_MAX_BOOT, "USV_ANA_MAX_BOOT") \
+  X(USV_ANA_MAX_Q, "USV_ANA_MAX_Q") \
+  X(USV_ANA_LDS_DOUBLES, "USV_ANA_LDS_DOUBLES") \
+  X(USV_ANA_SITE, "USV_ANA_SITE") \
+  X(USV_ANA_NAN_PROPAGATE, "USV_ANA_NAN_PROPAGATE") \
+  X(USV_ANA_NAN_IGNORE, "USV_ANA_NAN_IGNORE") \
   X(PPO_NIN, "PPO_NIN") \
   X(PPO_NH, "PPO_NH") \
   X(PPO_NA, "PPO_NA") \

@@ -3,7 +3,8 @@ them, scripts/rlgames_play_loopz.py:989-1030, 1380-1401) and the summary in its 
 (:1046-1073).  Pure numpy / stdlib: no device needed.
 
 The interval is the normal approximation mean +- 1.96 std / sqrt(count) on the finite values; the reference's
-2,000-resample bootstrap (:504-530) is not reproduced (evaluation section)."""
+2,000-resample bootstrap (:504-530) is not run here (evaluation section; the comparison stage resamples on
+the device, scenario.analysis)."""
 from __future__ import annotations
 
 import csv

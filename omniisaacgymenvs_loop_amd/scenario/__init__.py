@@ -1,5 +1,7 @@
 """Scenario tables: device mining (sampling), the table format (table), the teacher filter's selection (filter)
-the playlist runner (runner; needs a GPU, imported on first use) and the teacher-vs-student comparison (compare; its entry point is compare.compare)."""
+the playlist runner (runner; needs a GPU, imported on first use), the teacher-vs-student comparison (compare; its entry
+point is compare.compare) and the analysis of a comparison (analysis: bootstrap intervals and stratified effects on the
+device; its entry point is analysis.analyse)."""
 from .compare import (TailOverride, base_const_tail, base_const_tail_host, cmp_totals, pairing_info,
                       tail_params, wrong_random_tail_host)
 from .filter import CSV_COLUMNS, eval_rows, select_keep
