@@ -230,6 +230,15 @@ typedef struct usv_cfg {
   /* parity tests: with injected reset uniforms, take the spawn / disturbance-direction sin and cos from the
    * RU_TRIG slots (the reference's recorded CPU values) instead of usv_sincos_cr; 0 in training */
   int   inj_trig;
+  /* ---- GoToXY / KeepXY / TrackXYVelocity (USV_task_parameters.py:55-91, 130-177).  Their other constants live
+   * in the fields CaptureXY's share by name (GoToXYParameters / GoToXYReward are CaptureXY's ancestors):
+   * position_tolerance, kill_after_n, kill_dist, boundary_cost, goal_reward, time_reward, reward_mode,
+   * position_scale, exp_coeff, align_la1..3, the spawn disk and the curriculum block, each filled from the
+   * task's own defaults; KeepXY / TrackXYVelocity's reward mode and coefficient are tk_mode[0] / tk_coeff[0],
+   * TrackXYVelocity's tolerance tk_tol[0]. ---- */
+  float goal_random_velocity;   /* TrackXYVelocityParameters.goal_random_velocity */
+  int   kill_after_ge;          /* the goal counter kills at 1: goal_cnt >= kill_after_n (USV_go_to_xy.py:212-217,
+                                   USV_keep_xy.py:173-178), 0: goal_cnt > kill_after_n (USV_track_xy_velocity.py:123) */
 } usv_cfg_t;
 
 /* stage bits of ctl[USV_CTL_NAN_FLAG] / ppo_cfg_t.nan_flag (the reference's probe names) */
@@ -243,6 +252,12 @@ typedef struct usv_cfg {
 #define USV_TASK_CAPTURE_XY   0
 #define USV_TASK_GO_TO_POSE   1
 #define USV_TASK_TRACK_XYO    2
+#define USV_TASK_GO_TO_XY     3
+#define USV_TASK_KEEP_XY      4
+#define USV_TASK_TRACK_XY     5
+/* episode-sum slot of Penalties.action_variation_penalty for the non-CaptureXY kinds (their task sums take
+ * slots 0..4; ST_TIME_REWARD's slot is free for them) */
+#define USV_ST_ACTION_VARIATION 10
 /* per-env scratch rows of the two-phase TrackXYOVelocity step (usv_bufs_t.task_scratch) */
 #define USV_TS_LIN_REW 0
 #define USV_TS_PEN     1
@@ -276,7 +291,8 @@ typedef struct usv_bufs {
                                       env's obstacles, this cost, .fnorm) -- the field is never materialised */
   /* history */
   float *prev_cmd;                 /* [2][n] raw policy command (obs 23:25) */
-  float *prev_dist, *prev_head, *prev_pot, *prev_wz;
+  float *prev_dist, *prev_head, *prev_pot, *prev_wz;   /* non-CaptureXY kinds: prev_head holds the action sum of
+                                                          Penalties.prev_actions (penalize_action_variation) */
   int32_t *goal_cnt, *progress, *reset_buf;
   uint8_t *just_reset;
   int32_t *done_succ, *done_coll;
@@ -299,7 +315,8 @@ typedef struct usv_bufs {
   float   *dist;                   /* [USV_NDIST][n] disturbance parameters; NULL when no disturbance is on */
   const float *env_org;            /* [2][n] world x, y of each env's origin (RLTask._env_pos); NULL = 0 */
   float   *tgt_h;                  /* [n] GoToPose target heading / TrackXYO target angular velocity (tgt_x/y:
-                                      target position / target linear velocity); NULL for CaptureXY */
+                                      target position / target linear velocity); NULL for CaptureXY, may be NULL
+                                      for GoToXY / KeepXY / TrackXYVelocity (never read) */
   float   *task_scratch;           /* TrackXYO: [USV_TS_ROWS][n] + [ceil(n/256)] partial sums; else NULL */
   /* scene replay (USVVirtual._scene_replay_*, USV_Virtual.py:1329-1457): NULL scene = random spawns */
   const float *scene;              /* [n_scenes][USV_SCENE_STRIDE] (USV_SC_* layout) */

@@ -301,7 +301,10 @@ __global__ __launch_bounds__(kBlock) void k_reset(usv_cfg_t c, usv_bufs_t b, uin
         sy = r * sth;
         b.field_old_tgt[e] = tx;
         b.field_old_tgt[n + e] = ty;
-      } else if (c.task_kind == USV_TASK_GO_TO_POSE) {   // GoToPoseTask.get_spawns (USV_go_to_pose.py:256-319)
+      } else if (c.task_kind == USV_TASK_GO_TO_POSE || c.task_kind == USV_TASK_GO_TO_XY ||
+                 c.task_kind == USV_TASK_KEEP_XY) {
+        // GoToPoseTask.get_spawns (USV_go_to_pose.py:256-319); GoToXYTask / KeepXYTask.get_spawns are the same
+        // expressions on the same draws (USV_go_to_xy.py:257-321, USV_keep_xy.py:216-280)
         double rmax = c.spawn_rmax, rmin = c.spawn_rmin;
         if (c.curriculum_on) {   // :266-290, with the step the reference passes (USV_Virtual.py:1546)
           const double st = ref_step_of(c, b, step, 4);
@@ -315,8 +318,10 @@ __global__ __launch_bounds__(kBlock) void k_reset(usv_cfg_t c, usv_bufs_t b, uin
         if (inj_trig) { cth = U(RU_TRIG); sth = U(RU_TRIG + 1); }
         sx = r * cth + tx;
         sy = r * sth + ty;
-        b.prev_dist[e] = 0.f;                            // GoToPoseTask.reset: prev_position_dist = 0 (:227)
-      } else {                                           // TrackXYOVelocityTask.get_spawns (:203-219): env origin
+        // GoToPoseTask.reset: prev_position_dist = 0 (:227).  GoToXYReward.prev_position_error survives a reset
+        // (USV_task_rewards.py:126-151; the step zeroes the reset envs' distance reward instead)
+        if (c.task_kind != USV_TASK_GO_TO_XY) b.prev_dist[e] = 0.f;
+      } else {   // TrackXYOVelocityTask / TrackXYVelocityTask.get_spawns (:203-219, :158-170): env origin, yaw only
         sx = 0.f;
         sy = 0.f;
       }
@@ -385,8 +390,12 @@ __global__ __launch_bounds__(kBlock) void k_reset(usv_cfg_t c, usv_bufs_t b, uin
       b.prev_cmd[n + e] = 0.f;
       // ---- set_targets -> task.get_goals (not called under scene replay, :1613-1616) ----
       if (b.scene) {
-      } else if (c.task_kind != USV_TASK_TRACK_XYO) {   // static_obs.py:913-930, USV_go_to_pose.py:229-254
-        const float g = c.goal_random_position;
+      } else if (c.task_kind == USV_TASK_TRACK_XY) {    // USV_track_xy_velocity.py:144-156: target velocity
+        const float g = c.goal_random_velocity;
+        b.tgt_x[e] = U(RU_GOAL) * g * 2.0f - g;
+        b.tgt_y[e] = U(RU_GOAL + 1) * g * 2.0f - g;
+      } else if (c.task_kind != USV_TASK_TRACK_XYO) {   // static_obs.py:913-930, USV_go_to_pose.py:229-254,
+        const float g = c.goal_random_position;         // USV_go_to_xy.py:238-255, USV_keep_xy.py:197-214
         b.tgt_x[e] = U(RU_GOAL) * g * 2.0f - g;
         b.tgt_y[e] = U(RU_GOAL + 1) * g * 2.0f - g;
         if (c.task_kind == USV_TASK_GO_TO_POSE) b.tgt_h[e] = U(RU_GOAL_H) * USV_PI_F * 2.0f;
@@ -1245,6 +1254,13 @@ __global__ __launch_bounds__(64) void k_env_reward_late(usv_cfg_t c, usv_bufs_t 
 // (unwritten columns 0), update_kills(step) is the task's own, the reward is
 // task.compute_reward(current_state, actions) + penalties as calculate_metrics
 // (USV_Virtual.py:1628-1652) does for every task.
+// The same template carries GoToXY, KeepXY and TrackXYVelocity (USV_go_to_xy.py:96-218, USV_keep_xy.py:92-179,
+// USV_track_xy_velocity.py:76-128; rewards USV_task_rewards.py:117-153, 270-325): three task columns (two for
+// TrackXYVelocity), no third target component (tgt_h may be NULL), one launch.  Reproduced as the code runs, not as
+// its comments read: GoToXY's previous distance survives resets and the reset envs' distance reward is zeroed; its
+// boundary penalty reaches the episode sums only; KeepXY never increments its goal counter; GoToXY / KeepXY kill
+// at goal_cnt >= kill_after, TrackXYVelocity at > (usv_cfg_t.kill_after_ge).  Every non-CaptureXY kind takes
+// Penalties.penalize_action_variation (see p_actv below).
 // TrackXYOVelocity's angular error is reduced over ALL envs
 // (torch.square(err).sum(-1) of a 1-D tensor, :121-123), so its step is two
 // launches: this kernel writes per-block partial sums, k_track_finish completes.
@@ -1298,8 +1314,12 @@ __global__ __launch_bounds__(kBlock) void k_env_step_task(StepCfg ck, usv_bufs_t
     if (b.env_org) { orgx = b.env_org[ec]; orgy = b.env_org[nn + ec]; }
   }
   const int progress0 = b.progress[ec], goal_cnt0 = b.goal_cnt[ec];
-  const float tgx = b.tgt_x[ec], tgy = b.tgt_y[ec], tgh = b.tgt_h[ec];
+  constexpr bool kHasH = kKind == USV_TASK_GO_TO_POSE || kKind == USV_TASK_TRACK_XYO;   // the kinds with a tgt_h
+  const float tgx = b.tgt_x[ec], tgy = b.tgt_y[ec], tgh = kHasH ? b.tgt_h[ec] : 0.f;
   const float prev_pd = b.prev_dist[ec], prev_wz_mem = b.prev_wz[ec];
+  // Penalties.prev_actions as its action sum (penalize_action_variation); never cleared at a reset
+  const float prev_asum = c.pen_actv_kind ? b.prev_head[ec] : 0.f;
+  const bool rew_valid = b.ctl[USV_CTL_REW_VALID] != 0;
   // a reset env's first substep: the pre-reset inputs usv_reset kept
   const bool stl = c.stale_root && was_reset;
   float st_ub = 0.f, st_vb = 0.f, st_rb = 0.f, st_px = 0.f, st_py = 0.f;
@@ -1455,12 +1475,77 @@ __global__ __launch_bounds__(kBlock) void k_env_step_task(StepCfg ck, usv_bufs_t
   }
   if (c.pen_en_kind == PEN_SUM) p_en = -(pact0 + pact1) * c.pen_en_k + c.pen_en_c;
   else if (c.pen_en_kind == PEN_SUMSQ) p_en = -(pact0 * pact0 + pact1 * pact1) * c.pen_en_k + c.pen_en_c;
-  const float pen_sum = ((p_lin + p_ang) + p_angv) + p_en;
+  // penalize_action_variation (:497-506): sum(actions) - sum(prev_actions).  With penalties_use_thrust_u the
+  // reference hands compute_penalty its persistent thrust_cmds_unit tensor (USV_Virtual.py:1095, 1634-1639) and
+  // keeps that same object as prev_actions (:515), so the difference is identically 0; without it the actions
+  // are a fresh clone every step (:1050-1052) and the difference is the real one, across resets too
+  float p_actv = 0.f;
+  const float asum = cmd0 + cmd1;
+  if (c.pen_actv_kind) {
+    const float dsum = (c.pen_use_u || !pen_valid) ? 0.f : asum - prev_asum;
+    p_actv = pen_scalar(c.pen_actv_kind, c.pen_actv_k, c.pen_actv_x0, c.pen_actv_c, dsum);
+  }
+  const float pen_base = ((p_lin + p_ang) + p_angv) + p_en;
+  const float pen_sum = c.pen_actv_kind ? pen_base + p_actv : pen_base;
   const int tout = progress >= c.max_episode_length - 1;
-  float t_add[4];
+  float t_add[5];
+  t_add[4] = 0.f;
   float overall = 0.f;
   int goal_cnt = goal_cnt0, die = 0;
-  if (kKind == USV_TASK_GO_TO_POSE) {
+  if (kKind == USV_TASK_GO_TO_XY || kKind == USV_TASK_KEEP_XY) {
+    // GoToXYTask / KeepXYTask.get_state_observations (USV_go_to_xy.py:96-111, USV_keep_xy.py:92-105)
+    const float ex = tgx - pxn, ey = tgy - pyn;
+    const float theta = usv_atan2(hs, hc);
+    const float beta = usv_atan2(ey, ex);
+    const float alpha = fmodf((beta - theta) + USV_PI_F, USV_2PI_F) - USV_PI_F;
+    float sa, ca;
+    usv_sincos(alpha, &sa, &ca);
+    put(3, ca);
+    put(4, sa);
+    put(5, tnorm2(ex, ey));
+    // compute_reward (USV_go_to_xy.py:129-180, USV_keep_xy.py:123-141)
+    const float pdist = sqrtf(ex * ex + ey * ey);
+    const float bdist = pdist - c.kill_dist;
+    const float bpen = -usv_exp(-bdist / 0.25f) * c.boundary_cost;   // episode sums only, never the reward
+    if (kKind == USV_TASK_GO_TO_XY) {
+      const int gir = pdist < c.position_tolerance;
+      goal_cnt = goal_cnt0 * gir + gir;
+      // GoToXYReward.compute_reward (USV_task_rewards.py:117-153): the previous error is a per-env value that
+      // no reset clears; the task zeroes the distance reward of the envs reset this step (:161)
+      const float prev_err = rew_valid ? prev_pd : pdist;
+      float dist_r;
+      if (c.reward_mode == 0) dist_r = c.position_scale * (prev_err - pdist);
+      else if (c.reward_mode == 1) dist_r = c.position_scale * (prev_err * prev_err - pdist * pdist);
+      else dist_r = c.position_scale * (usv_exp(-pdist / c.exp_coeff) - usv_exp(-prev_err / c.exp_coeff));
+      if (was_reset) dist_r = 0.f;
+      const float herr = fabsf(alpha), h2 = herr * herr;
+      const float align_r = c.align_la1 * (usv_exp(c.align_la2 * (h2 * h2)) + usv_exp(c.align_la3 * h2));
+      if (mine) b.prev_dist[e] = pdist;
+      overall = ((dist_r + align_r) + (float)goal_cnt * c.goal_reward) + c.time_reward;
+      t_add[0] = dist_r; t_add[1] = align_r; t_add[2] = pdist; t_add[3] = bpen; t_add[4] = bdist;
+    } else {
+      // KeepXYReward.compute_reward (:270-287); _goal_reached is never incremented (goal_cnt stays 0)
+      overall = task_term(c.tk_mode[0], pdist, c.tk_coeff[0]);
+      t_add[0] = overall; t_add[1] = pdist; t_add[2] = bpen; t_add[3] = bdist;
+    }
+    // update_kills (USV_go_to_xy.py:182-218, USV_keep_xy.py:143-179)
+    const float kd = c.curriculum_on ? (float)curriculum_lerp(c, ref_step_of(c, b, step, 5), c.cur_kill_dist,
+                                                              c.kill_dist_d)
+                                     : c.kill_dist;
+    die = (pdist > kd) || (c.kill_after_ge ? goal_cnt >= c.kill_after_n : goal_cnt > c.kill_after_n);
+  } else if (kKind == USV_TASK_TRACK_XY) {
+    // TrackXYVelocityTask.get_state_observations / compute_reward / update_kills (USV_track_xy_velocity.py:76-128)
+    const float lex = tgx - vxn, ley = tgy - vyn;
+    put(3, lex);
+    put(4, ley);
+    const float pos_d = sqrtf(pxn * pxn + pyn * pyn);
+    const float lin_d = sqrtf(lex * lex + ley * ley);
+    const int gir = lin_d < c.tk_tol[0];
+    goal_cnt = goal_cnt0 * gir + gir;
+    overall = task_term(c.tk_mode[0], lin_d, c.tk_coeff[0]);   // TrackXYVelocityReward (:308-325)
+    die = (pos_d > c.kill_dist) || (c.kill_after_ge ? goal_cnt >= c.kill_after_n : goal_cnt > c.kill_after_n);
+    t_add[0] = overall; t_add[1] = lin_d; t_add[2] = 0.f; t_add[3] = 0.f;
+  } else if (kKind == USV_TASK_GO_TO_POSE) {
     // GoToPoseTask.get_state_observations (:89-130)
     const float ex = tgx - pxn, ey = tgy - pyn;
     const float theta = usv_atan2(hs, hc);
@@ -1525,8 +1610,9 @@ __global__ __launch_bounds__(kBlock) void k_env_step_task(StepCfg ck, usv_bufs_t
     b.prev_cmd[e] = prev_cmd0;
     b.prev_cmd[nn + e] = prev_cmd1;
     b.prev_wz[e] = wzn;
+    if (c.pen_actv_kind) b.prev_head[e] = asum;
     b.just_reset[e] = 0;
-    if (kKind == USV_TASK_GO_TO_POSE) {
+    if (kKind != USV_TASK_TRACK_XYO) {   // TrackXYOVelocity: k_track_finish
       const float rew = overall + pen_sum;
       const int rb = c.fixed_horizon_eval ? tout : (tout ? 1 : die);
       b.goal_cnt[e] = goal_cnt;
@@ -1539,7 +1625,8 @@ __global__ __launch_bounds__(kBlock) void k_env_step_task(StepCfg ck, usv_bufs_t
       float add[USV_NSTAT];
 #pragma unroll
       for (int q = 0; q < USV_NSTAT; ++q) add[q] = 0.f;
-      add[0] = t_add[0]; add[1] = t_add[1]; add[2] = t_add[2]; add[3] = t_add[3];
+      add[0] = t_add[0]; add[1] = t_add[1]; add[2] = t_add[2]; add[3] = t_add[3]; add[4] = t_add[4];
+      add[USV_ST_ACTION_VARIATION] = p_actv;
       add[ST_ANGULAR_VEL_PENALTY] = p_ang;
       add[ST_ANGULAR_VEL_VARIATION_PENALTY] = p_angv;
       add[ST_ENERGY_PENALTY] = p_en;
@@ -1551,7 +1638,7 @@ __global__ __launch_bounds__(kBlock) void k_env_step_task(StepCfg ck, usv_bufs_t
       add[ST_U_SUM] = unit0 + unit1;
 #pragma unroll
       for (int q = 0; q < USV_NSTAT; ++q)
-        if (q != ST_SUCCESS && q != ST_COLLISION && (kKind == USV_TASK_GO_TO_POSE || (q != 2 && q != 3)))
+        if (q != ST_SUCCESS && q != ST_COLLISION && (kKind != USV_TASK_TRACK_XYO || (q != 2 && q != 3)))
           b.stats[q * nn + e] = sums[q] + add[q];
     }
   }
@@ -1575,7 +1662,7 @@ __global__ __launch_bounds__(kBlock) void k_env_step_task(StepCfg ck, usv_bufs_t
     uint32_t bits = ((nonfinite(cmd0) | nonfinite(cmd1)) ? USV_NAN_ACTIONS : 0u) |
                     ((nonfinite(pxn) | nonfinite(pyn) | nonfinite(yawn) | nonfinite(vxn) | nonfinite(vyn) |
                       nonfinite(wzn)) ? USV_NAN_STATE : 0u) |
-                    ((kKind == USV_TASK_GO_TO_POSE && nonfinite(overall + pen_sum)) ? USV_NAN_REWARD : 0u);
+                    ((kKind != USV_TASK_TRACK_XYO && nonfinite(overall + pen_sum)) ? USV_NAN_REWARD : 0u);
     nan_report(&b.ctl[USV_CTL_NAN_FLAG], (mine ? bits : 0u) | (obad ? USV_NAN_OBS : 0u));
   }
   if (blockIdx.x == 0 && tid == 0) b.ctl[USV_CTL_STEPPED] = 1;
@@ -1913,7 +2000,8 @@ int usv_env_step_part(const usv_cfg_t *cfg, const usv_bufs_t *b, const float *ac
   if (cfg->priv_dim != 4 && cfg->priv_dim != 8) return 3;
   if (cfg->task_kind != USV_TASK_CAPTURE_XY) {
     // GoToPose / TrackXYOVelocity: no potential field, so no split step
-    if (part != 0 || !b->tgt_h) return 1;
+    const int kind = cfg->task_kind;
+    if (part != 0 || ((kind == USV_TASK_GO_TO_POSE || kind == USV_TASK_TRACK_XYO) && !b->tgt_h)) return 1;
     if (step_has_dist(*cfg) && !b->dist) return 4;
     if (cfg->task_kind == USV_TASK_TRACK_XYO && !b->task_scratch) return 1;
     const StepK k = step_constants(*cfg);
@@ -1933,6 +2021,15 @@ int usv_env_step_part(const usv_cfg_t *cfg, const usv_bufs_t *b, const float *ac
       USV_CHECK_LAUNCH();
       hipLaunchKernelGGL(st ? k_track_finish<true> : k_track_finish<false>, dim3(grid), dim3(kBlock), 0, s, *cfg, *b,
                          grid);
+    } else if (kind == USV_TASK_GO_TO_XY || kind == USV_TASK_KEEP_XY || kind == USV_TASK_TRACK_XY) {
+#define USV_TASK_KERN(KIND)                                                                                       \
+  (st ? (ij ? k_env_step_task<KIND, true, true> : k_env_step_task<KIND, true, false>)                               \
+      : (ij ? k_env_step_task<KIND, false, true> : k_env_step_task<KIND, false, false>))
+      auto kern = kind == USV_TASK_GO_TO_XY ? USV_TASK_KERN(USV_TASK_GO_TO_XY)
+                  : kind == USV_TASK_KEEP_XY ? USV_TASK_KERN(USV_TASK_KEEP_XY) : USV_TASK_KERN(USV_TASK_TRACK_XY);
+#undef USV_TASK_KERN
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, s, StepCfg{*cfg, k}, *b, actions, lut_dev, action_bias, seed,
+                         step, u_inject);
     } else {
       return 1;
     }

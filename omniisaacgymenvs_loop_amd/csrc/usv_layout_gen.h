@@ -52,6 +52,10 @@
   X(USV_TASK_CAPTURE_XY, "USV_TASK_CAPTURE_XY") \
   X(USV_TASK_GO_TO_POSE, "USV_TASK_GO_TO_POSE") \
   X(USV_TASK_TRACK_XYO, "USV_TASK_TRACK_XYO") \
+  X(USV_TASK_GO_TO_XY, "USV_TASK_GO_TO_XY") \
+  X(USV_TASK_KEEP_XY, "USV_TASK_KEEP_XY") \
+  X(USV_TASK_TRACK_XY, "USV_TASK_TRACK_XY") \
+  X(USV_ST_ACTION_VARIATION, "USV_ST_ACTION_VARIATION") \
   X(USV_TS_LIN_REW, "USV_TS_LIN_REW") \
   X(USV_TS_PEN, "USV_TS_PEN") \
   X(USV_TS_LIN_OK, "USV_TS_LIN_OK") \
@@ -491,6 +495,8 @@
   X(offsetof(usv_cfg_t, kill_dist_d), "usv_cfg.kill_dist_d") \
   X(offsetof(usv_cfg_t, stale_root), "usv_cfg.stale_root") \
   X(offsetof(usv_cfg_t, inj_trig), "usv_cfg.inj_trig") \
+  X(offsetof(usv_cfg_t, goal_random_velocity), "usv_cfg.goal_random_velocity") \
+  X(offsetof(usv_cfg_t, kill_after_ge), "usv_cfg.kill_after_ge") \
   X(sizeof(usv_bufs_t), "sizeof usv_bufs") \
   X(offsetof(usv_bufs_t, n), "usv_bufs.n") \
   X(offsetof(usv_bufs_t, pad0), "usv_bufs.pad0") \

@@ -251,6 +251,9 @@ def build_usv_cfg(task_cfg: Dict[str, Any]) -> UsvCfg:
     rp = dict(_REWARD_DEFAULTS)
     if name == "CaptureXY":
         rp.update(env["reward_parameters"])
+    elif name == "GoToXY":   # GoToXYReward shares CaptureXYReward's field names, with its own defaults
+        rp = dict(_XY_REWARD)
+        rp.update(env.get("reward_parameters", {}) or {})
     rm = rp["reward_mode"].lower()
     if rm not in ("linear", "square", "exponential"):
         raise ValueError("Linear, Square and Exponential are the only currently supported mode.")
@@ -280,7 +283,7 @@ def build_usv_cfg(task_cfg: Dict[str, Any]) -> UsvCfg:
         raise ValueError("linear-velocity penalty must be the norm form")
     if c.pen_en_kind not in (0, PEN["PEN_SUM"], PEN["PEN_SUMSQ"]):
         raise ValueError("energy penalty must be a sum form")
-    if c.pen_actv_kind != 0:
+    if c.pen_actv_kind != 0 and name == "CaptureXY":
         raise NotImplementedError("penalize_action_variation is not on the CaptureXY hot path")
     c.pen_use_u = int(bool(ap.get("penalties_use_thrust_u", True)))
 
@@ -352,7 +355,8 @@ def raise_nan_flag(bits: int, where: str) -> None:
                        f"set USV_NAN_PROBE=0 to disable)")
 
 
-TASK_KINDS = {"CaptureXY": 0, "GoToPose": 1, "TrackXYOVelocity": 2}   # USV_TASK_* (include/usv_hip.h)
+# USV_TASK_* (include/usv_hip.h): the six tasks of the reference's factory (USV_task_factory.py:59-64)
+TASK_KINDS = {"CaptureXY": 0, "GoToPose": 1, "TrackXYOVelocity": 2, "GoToXY": 3, "KeepXY": 4, "TrackXYVelocity": 5}
 _MODES = {"linear": 0, "square": 1, "exponential": 2}
 # GoToPoseParameters / TrackXYOVelocityParameters and their reward dataclasses
 # (USV_task_parameters.py:74-148, USV_task_rewards.py:160-393)
@@ -372,6 +376,21 @@ _TRACK_REWARD = dict(linear_reward_mode="exponential", angular_reward_mode="expo
                      linear_scale=1.0, angular_scale=1.0)
 
 
+# GoToXYParameters / KeepXYParameters (USV_task_parameters.py:55-91, 130-166: the same fields and defaults),
+# GoToXYReward, KeepXYReward, TrackXYVelocityParameters / Reward (USV_task_rewards.py:93-105, 252-258, 290-296)
+_XY_DEFAULTS = dict(position_tolerance=0.1, kill_after_n_steps_in_tolerance=1, goal_random_position=0.0,
+                    max_spawn_dist=11.0, min_spawn_dist=0.5, kill_dist=20.0, boundary_cost=25.0, goal_reward=100.0,
+                    time_reward=-0.1, spawn_curriculum=False, spawn_curriculum_min_dist=0.2,
+                    spawn_curriculum_max_dist=3.0, spawn_curriculum_kill_dist=30.0, spawn_curriculum_mode="linear",
+                    spawn_curriculum_warmup=250, spawn_curriculum_end=1000)
+_XY_REWARD = dict(reward_mode="exponential", position_scale=1.0, exponential_reward_coeff=0.15, align_la1=0.05,
+                  align_la2=-10.0, align_la3=-0.1)
+_KEEP_REWARD = dict(reward_mode="linear", exponential_reward_coeff=0.25)
+_TRACK_XY_DEFAULTS = dict(lin_vel_tolerance=0.01, kill_after_n_steps_in_tolerance=50, goal_random_velocity=0.75,
+                          kill_dist=500.0)
+_TRACK_XY_REWARD = dict(reward_mode="exponential", exponential_reward_coeff=0.25)
+
+
 def _mode(v: str) -> int:
     m = str(v).lower()
     if m not in _MODES:
@@ -379,26 +398,59 @@ def _mode(v: str) -> int:
     return _MODES[m]
 
 
+def _spawn_curriculum(c: UsvCfg, tp: Dict[str, Any]) -> None:
+    """The spawn curriculum block of GoToPose / GoToXY / KeepXYParameters (USV_task_parameters.py:70-91, 107-128,
+    145-166): linear mode only, as the reference asserts."""
+    if not bool(tp.get("spawn_curriculum", False)):
+        return
+    if str(tp["spawn_curriculum_mode"]).lower() != "linear":
+        raise AssertionError("Linear is the only currently supported mode.")
+    c.curriculum_on = 1
+    c.cur_min_dist = float(tp["spawn_curriculum_min_dist"])
+    c.cur_max_dist = float(tp["spawn_curriculum_max_dist"])
+    c.cur_kill_dist = float(tp["spawn_curriculum_kill_dist"])
+    c.cur_warmup = float(int(tp["spawn_curriculum_warmup"]))
+    c.cur_end = float(int(tp["spawn_curriculum_end"]))
+    c.min_spawn_d, c.max_spawn_d = float(tp["min_spawn_dist"]), float(tp["max_spawn_dist"])
+    c.kill_dist_d = float(tp["kill_dist"])
+
+
+def _xy_task_cfg(c: UsvCfg, name: str, env: Dict[str, Any]) -> Dict[str, Any]:
+    """GoToXY / KeepXY / TrackXYVelocity constants from the task's own parameter defaults.  GoToXY's reward
+    parameters are read by the common parser (GoToXYReward has CaptureXYReward's field names)."""
+    if name == "TrackXYVelocity":
+        tp = dict(_TRACK_XY_DEFAULTS)
+        tp.update(env["task_parameters"])
+        rp = dict(_TRACK_XY_REWARD)
+        rp.update(env.get("reward_parameters", {}) or {})
+        c.tk_tol[0] = tp["lin_vel_tolerance"]
+        c.goal_random_velocity = tp["goal_random_velocity"]
+        c.kill_after_ge = 0                       # goal_cnt > kill_after (USV_track_xy_velocity.py:123-127)
+        tp.setdefault("position_tolerance", 0.0)  # read by the common parser, unused by this task
+    else:
+        tp = dict(_XY_DEFAULTS)
+        tp.update(env["task_parameters"])
+        rp = dict(_KEEP_REWARD)
+        rp.update(env.get("reward_parameters", {}) or {})
+        _spawn_curriculum(c, tp)
+        c.kill_after_ge = 1                       # goal_cnt >= kill_after (USV_go_to_xy.py:212-217)
+    if name != "GoToXY":
+        c.tk_mode[0] = _mode(rp["reward_mode"])
+        c.tk_coeff[0] = rp["exponential_reward_coeff"]
+    return tp
+
+
 def _pose_task_cfg(c: UsvCfg, name: str, env: Dict[str, Any]) -> Dict[str, Any]:
     """GoToPose / TrackXYOVelocity constants; the task's own parameter defaults
     replace CaptureXY's (env.task_parameters / env.reward_parameters override)."""
+    if name in ("GoToXY", "KeepXY", "TrackXYVelocity"):
+        return _xy_task_cfg(c, name, env)
     if name == "GoToPose":
         tp = dict(_POSE_DEFAULTS)
         tp.update(env["task_parameters"])
         rp = dict(_POSE_REWARD)
         rp.update(env.get("reward_parameters", {}) or {})
-        if bool(tp.get("spawn_curriculum", False)):
-            # GoToPoseParameters (USV_task_parameters.py:107-128): linear mode only, as the reference asserts
-            if str(tp["spawn_curriculum_mode"]).lower() != "linear":
-                raise AssertionError("Linear is the only currently supported mode.")
-            c.curriculum_on = 1
-            c.cur_min_dist = float(tp["spawn_curriculum_min_dist"])
-            c.cur_max_dist = float(tp["spawn_curriculum_max_dist"])
-            c.cur_kill_dist = float(tp["spawn_curriculum_kill_dist"])
-            c.cur_warmup = float(int(tp["spawn_curriculum_warmup"]))
-            c.cur_end = float(int(tp["spawn_curriculum_end"]))
-            c.min_spawn_d, c.max_spawn_d = float(tp["min_spawn_dist"]), float(tp["max_spawn_dist"])
-            c.kill_dist_d = float(tp["kill_dist"])
+        _spawn_curriculum(c, tp)
         c.tk_mode[0], c.tk_mode[1] = _mode(rp["position_reward_mode"]), _mode(rp["heading_reward_mode"])
         c.tk_coeff[0] = rp["position_exponential_reward_coeff"]
         c.tk_coeff[1] = rp["heading_exponential_reward_coeff"]
@@ -440,10 +492,16 @@ def stat_names(c: UsvCfg):
     """(extras["episode"] key, episode-sum slot) pairs in the reference's dict order:
     task.create_stats, Penalties.get_stats_name, success/collision, state statistics
     (USV_Virtual.py:584-601).  CaptureXY keeps the fixed 28-key layout of _abi.STAT_NAMES."""
-    from .._abi import STAT_KEYS_ENUM as S, STAT_NAMES
+    from .._abi import DEFINES, STAT_KEYS_ENUM as S, STAT_NAMES
     if c.task_kind == 0:
         return list(zip(STAT_NAMES, range(len(STAT_NAMES))))
+    # GoToXY / KeepXY / TrackXYVelocity: create_stats order = slot order (USV_go_to_xy.py:64-82,
+    # USV_keep_xy.py:62-78, USV_track_xy_velocity.py:50-62)
+    own = {3: ["distance_reward", "alignment_reward", "position_error", "boundary_penalty", "boundary_dist"],
+           4: ["position_reward", "position_error", "boundary_penalty", "boundary_dist"],
+           5: ["velocity_reward", "velocity_error"]}
     task = (["position_reward", "position_error", "heading_reward", "heading_error"] if c.task_kind == 1 else
+            own[c.task_kind] if c.task_kind in own else
             ["linear_velocity_reward", "linear_velocity_error", "angular_velocity_reward", "angular_velocity_error"])
     slot = ({"position_reward": 0, "heading_reward": 1, "position_error": 2, "heading_error": 3} if c.task_kind == 1
             else {k: i for i, k in enumerate(task)})
@@ -454,6 +512,8 @@ def stat_names(c: UsvCfg):
         out.append(("angular_vel_variation_penalty", S["ST_ANGULAR_VEL_VARIATION_PENALTY"]))
     if c.pen_en_kind:
         out.append(("energy_penalty", S["ST_ENERGY_PENALTY"]))
+    if c.pen_actv_kind:
+        out.append(("action_variation_penalty", DEFINES["USV_ST_ACTION_VARIATION"]))
     for k in ("success", "collision", "normed_linear_vel", "normed_angular_vel", "cmd_neg_rate", "u_mean",
               "u_low_rate", "u_sum"):
         out.append((k, S["ST_" + k.upper()]))

@@ -35,6 +35,8 @@ NU_RESET = DEFINES["USV_NU_RESET"]
 NU_STEP = DEFINES["USV_NU_STEP"]
 NDIST = enum_values("usv_dist_row")["USV_NDIST"]
 TASK_CAPTURE_XY, TASK_TRACK_XYO = DEFINES["USV_TASK_CAPTURE_XY"], DEFINES["USV_TASK_TRACK_XYO"]
+# the kinds whose target has no third component (usv_bufs_t.tgt_h = NULL)
+TASKS_WITHOUT_TGT_H = (DEFINES["USV_TASK_GO_TO_XY"], DEFINES["USV_TASK_KEEP_XY"], DEFINES["USV_TASK_TRACK_XY"])
 TS_ROWS = DEFINES["USV_TS_ROWS"]
 CTL_N = DEFINES["USV_CTL_N"]
 
@@ -136,6 +138,8 @@ class USVVirtual:
         # TrackXYOVelocity's two-phase step: per-env rows + per-256-env-block partial sums
         self.task_scratch = (Z(TS_ROWS * n + (n + 255) // 256, **f32) if self.cfg.task_kind == TASK_TRACK_XYO
                              else None)
+        if self.cfg.task_kind in TASKS_WITHOUT_TGT_H:
+            self.tgt_h = None   # the slab row stays unused
         self._has_field = self.cfg.task_kind == TASK_CAPTURE_XY
         self.field = Z((n if self._has_field else 1, FIELD_STRIDE), **f32)   # tiled raw cost of the field
         self.ibuf[2] = 1                               # RLTask.cleanup: reset_buf = ones
@@ -280,7 +284,7 @@ class USVVirtual:
         b.grid_lin = p(self.grid_lin) if self.grid_lin is not None else None
         b.dist = p(self.dist) if self.dist is not None else None
         b.env_org = p(self.env_org)
-        b.tgt_h = p(self.tgt_h)
+        b.tgt_h = p(self.tgt_h) if self.tgt_h is not None else None
         b.stale = p(self.stale)
         b.task_scratch = p(self.task_scratch) if self.task_scratch is not None else None
         if self.scene is not None:
