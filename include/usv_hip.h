@@ -896,7 +896,10 @@ int ppo_prepare(const ppo_cfg_t *cfg, const float *params, const double *obs_rms
  * the LR schedule used (after the all-reduce), as kls[] of the reference log.
  * grad has ppo_grad_floats() entries: [0, NPARAM) gradient, [NPARAM] kl, then
  * the reduce kernel's per-workgroup squared norms; norm_from_partials = 1 (only
- * when grad was NOT all-reduced) takes the clip norm from those. */
+ * when grad was NOT all-reduced) takes the clip norm from those.  Its last 128 x 129
+ * floats (16-byte aligned) are the chained update's W2 image: written by the
+ * speculative step of ppo_minibatch_fused / _fused_dp, copied into LDS by the next
+ * call of the chain, which therefore needs the same, 16-byte aligned grad. */
 int ppo_minibatch_grad(const ppo_cfg_t *cfg, const float *params, double *obs_rms,
                        const double *val_rms, int update_obs_rms, int mb_index,
                        const float *exp_obs, const float *exp_act, const float *exp_nlp,

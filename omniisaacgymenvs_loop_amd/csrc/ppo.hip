@@ -1028,6 +1028,17 @@ constexpr int RD_KB = 16;                               // loads in flight per l
 constexpr int RED_BLOCKS = (PPO_NPARAM + 5 + RD_P - 1) / RD_P;
 static_assert(RD_P % 4 == 0 && 64 % RD_L == 0 && RD_P <= RD_TB, "reduce geometry");
 static_assert(RED_BLOCKS <= 256, "chunk squares: one per thread of waves 0-3");
+// The W2 image, the last floats of grad[] (behind the chunk squares, 16-byte aligned): W2 in the gradient
+// kernel's LDS layout, image[j HS + k] = W2[j][k].  The speculative step of k_reduce_partials writes it beside
+// bank cur, and the next minibatch's chained gradient kernel copies it flat into s.w2 by LDS-DMA (64 pieces
+// of 1 KB and one of 512 B) instead of staging W2 through registers.  The pad words (k = NH of each row) are
+// never written and no product reads them.
+constexpr int W2IMG_FLOATS = (NH * HS + 3) & ~3;
+constexpr int W2IMG_OFF = (PPO_NPARAM + 8 + RED_BLOCKS + 3) & ~3;
+constexpr int W2IMG_PIECES = W2IMG_FLOATS / 256;               // whole wave-instructions (64 lanes x 16 B)
+constexpr int W2IMG_LAST_LANES = W2IMG_FLOATS % 256 / 4;       // lanes of the last, partial one
+static_assert(W2IMG_FLOATS == NH * HS && W2IMG_PIECES % 8 == 0 && W2IMG_LAST_LANES > 0 && W2IMG_LAST_LANES < 64,
+              "W2 image: the copy covers s.w2 exactly, 8 waves x whole pieces + one partial piece");
 
 // ---- Adam (torch.optim.Adam, amsgrad off), shared by k_apply, the speculative step of
 // k_reduce_partials and the redo of a clipped step in the chained gradient kernel ----
@@ -1125,7 +1136,7 @@ struct ChainIn {
 constexpr int XG = XS;          // row stride of x / W1 in the gradient kernel's LDS
 constexpr int GX = ((RB * XG + GTB - 1) / GTB) * GTB;
 struct GradSmem {
-  float w2[NH * HS];              // W2[j][k]
+  alignas(16) float w2[NH * HS];  // W2[j][k] (16-byte aligned: the LDS-DMA copy of the W2 image lands here)
   float w1[NH * XG];              // W1[j][k], k 33, 34 = 0
   float x[GX];                    // normalised obs (dW1 operand); [RB * XG, GX) staging overflow slots
   float h1[RB * HS];              // tanh layer 1, later dz1
@@ -1243,6 +1254,20 @@ __device__ __forceinline__ f32x4v ld4_sc1(__amdgpu_buffer_rsrc_t r, uint32_t byt
   return __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, AUX_SC1));
 }
 
+// One LDS-DMA wave-instruction: each active lane's 16 bytes at src go to LDS byte address lds_dst (wave-uniform)
+// + 16 lane, with no register in between.  Issued as inline assembly, so the compiler's wait counting does not
+// see it: a __syncthreads() stays a bare barrier and the counted waits of the ordinary loads stay counted (with
+// the builtin, every later vmcnt wait and every __syncthreads() drains the copy: vmcnt(0)).  The issuer waits
+// for it itself (s_waitcnt vmcnt(0), then a barrier) before any wave reads the destination.
+__device__ __forceinline__ void lds_dma16(const float *src, uint32_t lds_dst) {
+  uint32_t keep;
+  __asm__ volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
+                   "s_mov_b32 m0, %0"
+                   : "=&s"(keep)
+                   : "v"(src), "s"(lds_dst)
+                   : "memory");
+}
+
 // chained update, clipping due: minibatch k-1's step redone from bank prev with the clip
 // coefficient, straight into this workgroup's LDS weights (and sigma into ls0 / ls1);
 // workgroup (q / GTB) % grid writes parameter chunk q / GTB of the redone state over bank cur
@@ -1325,7 +1350,10 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
   // of one row, conflict-free at the odd row stride (16-byte loads would leave 4-word strided writes)
   constexpr int NW1G = (NH * XG + GTB - 1) / GTB, NTLG = (TAIL + GTB - 1) / GTB, NW2F = NH * NH / GTB;
   static_assert(NH * NH % GTB == 0, "staging trip counts");
-  float w2f[NW2F];
+  // kImg (the chained single-rank and peer-exchange launches): W2 comes from the image the previous
+  // minibatch's reduction wrote behind ch.grad's chunk squares (W2IMG_OFF), by LDS-DMA; no w2f, no commit
+  constexpr bool kImg = kChain && !kColl && !kFold;
+  float w2f[kImg ? 1 : NW2F];
   float w1r[NW1G], tlr[NTLG];
   // chained update: minibatch k-1's optimiser scalars (lanes 0-7) and KL (lane 8) as VECTOR loads,
   // the first in flight -- scalar loads here would share lgkmcnt with the LDS staging writes and
@@ -1346,21 +1374,23 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
   }
   const float b1r = P[PPO_OFF_B1 + (tid & (NH - 1))];
   // log-sigma as a vector load too (read out by readlane where the losses use it)
-  const float lsv = P[PPO_OFF_SIGMA + (lane & 1)];
+  float lsv;
+  if constexpr (!kImg) lsv = P[PPO_OFF_SIGMA + (lane & 1)];
   float lsig0 = 0.f, lsig1 = 0.f;
   // chained update: minibatch k-1's chunk squares (its clip norm)
   float csq = 0.f;
   if constexpr (kChain) csq = ch.grad[PPO_NPARAM + 8 + min(tid, RED_BLOCKS - 1)];
   // per-row loss inputs, lane = row (waves 0 and 1 use them: the actor / the critic side)
   RowIn ri;
-  {
+  const auto load_rows = [&] {
     const size_t row = (size_t)rb0 + (lane & (RB - 1));
     ri.act0 = e_act[row * 2]; ri.act1 = e_act[row * 2 + 1];
     ri.nlp = e_nlp[row]; ri.adv = e_adv[row];
     ri.val = e_val[row]; ri.ret = e_ret[row];
     ri.mu0 = e_mu[row * 2]; ri.mu1 = e_mu[row * 2 + 1];
     ri.sg0 = e_sigma[row * 2]; ri.sg1 = e_sigma[row * 2 + 1];
-  }
+  };
+  if constexpr (!kImg) load_rows();
   // obs rows and the running statistics (always loaded; obs_rms is non-null, checked on the host)
   constexpr int NU = (RB * XG + GTB - 1) / GTB;
   float xo[NU];
@@ -1374,8 +1404,28 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
   }
   // W2 (64 KB of the 85 KB) issued LAST: the staging of x / W1 / biases and layer 1 wait only for the
   // loads ahead of it (counted vmcnt waits), W2 lands during layer 1 and is committed after it
+  if constexpr (kImg) {
+    // The loads the losses use first (log-sigma and the per-row inputs: 8 load instructions) go between the
+    // staging's loads and the copy.  The compiler counts its waits without the copy's wave-instructions
+    // (lds_dma16), so the staging's last wait leaves 8 operations outstanding: with these 8 behind the
+    // staging's loads they are the wave's 8 whole pieces, not loads the staging needs.  Wave 7 has a ninth
+    // piece, the last 512 B, issued first: the one part of the copy its staging waits for.
+    lsv = P[PPO_OFF_SIGMA + (lane & 1)];
+    load_rows();
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    const uint32_t w2lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float *)s.w2;
+    const float *img = ch.grad + W2IMG_OFF + lane * 4;
+    if (wu == GTB / 64 - 1 && lane < W2IMG_LAST_LANES)       // the last 512 B
+      lds_dma16(img + W2IMG_PIECES * 256, w2lds + W2IMG_PIECES * 1024);
 #pragma unroll
-  for (int u = 0; u < NW2F; ++u) w2f[u] = P[PPO_OFF_W2 + tid + u * GTB];
+    for (int u = 0; u < W2IMG_PIECES / (GTB / 64); ++u) {   // wave w: pieces w, w + 8, ...
+      const int pc = wu + (GTB / 64) * u;
+      lds_dma16(img + pc * 256, w2lds + pc * 1024);
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < NW2F; ++u) w2f[u] = P[PPO_OFF_W2 + tid + u * GTB];
+  }
   __builtin_amdgcn_sched_barrier(0);   // every load above is issued before anything waits
 #pragma unroll
   for (int u = 0; u < NW1G; ++u)
@@ -1431,6 +1481,10 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
     }
     if (kColl || coef < 1.0f) {   // uniform over the launch
       slow = true;
+      if constexpr (kImg) {   // redo_step writes s.w2 itself: no wave's copy of the image may land after it
+        __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+      }
       float op[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) op[q] = lane_of(q);
@@ -1452,8 +1506,11 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
     for (int r = 0; r < 16; ++r) s.h1[crow(r, h) * HS + n0 + i] = fast_tanh(acc[r] + bj);
   }
   USV_PHASE(ppo, 9);
-  // W2 into LDS (waves 4-7 do it while 0-3 run layer 1; each thread commits its own loads)
-  if (!slow) {
+  // W2 into LDS (waves 4-7 do it while 0-3 run layer 1; each thread commits its own loads).  kImg: nothing
+  // to commit -- each wave waits here for its pieces of the image copy, the only wait that covers them
+  if constexpr (kImg) {
+    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  } else if (!slow) {
 #pragma unroll
     for (int u = 0; u < NW2F; ++u) {
       const int e = tid + u * GTB;
@@ -2074,6 +2131,10 @@ __global__ __launch_bounds__(RD_TB) void k_reduce_partials(const float *__restri
         float pn, mn, vn;
         adam_one(c, ak, s, p_old, m_old, v_old, pn, mn, vn);
         a.P1[pq] = pn; a.m1[pq] = mn; a.v1[pq] = vn;
+        if (pq >= PPO_OFF_W2 && pq < PPO_OFF_B2) {   // the W2 image the next gradient kernel copies into LDS
+          const int e = pq - PPO_OFF_W2;
+          grad[W2IMG_OFF + (e / NH) * HS + e % NH] = pn;
+        }
       }
     } else if (slot < PPO_NPARAM + 5) {
       const int q = slot - PPO_NPARAM;
@@ -2317,7 +2378,8 @@ static int fused_launch(const ppo_cfg_t *cfg, const ppo_adam_banks_t *banks, con
   if (!cfg || !obs_rms || !grad || !partials || !work || seq < 0) return 1;
   if (!banks_ok(banks)) return 4;
   if (cfg->minibatch % RB != 0 || ppo_partials_floats(cfg->minibatch) <= 0) return 2;   // no partial layout
-  if (reinterpret_cast<uintptr_t>(partials) & 15u) return 3;
+  // (grad: the chained gradient kernel copies the W2 image behind the chunk squares in 16-byte pieces)
+  if ((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(grad)) & 15u) return 3;
   if (dp) {
     if (dp->world < 1 || dp->world > PPO_DP_MAX || dp->rank < 0 || dp->rank >= dp->world || !dp->clock || !dp->err)
       return 5;
@@ -2537,7 +2599,8 @@ int ppo_partials_floats(int minibatch) {
   const long long f = (long long)part_body_floats(minibatch / RB) + FOLD_G * FOLD_CTL_STRIDE;
   return f > 0x7fffffffLL ? -1 : (int)f;
 }
-int ppo_grad_floats(void) { return PPO_NPARAM + 8 + RED_BLOCKS; }
+// gradient + loss sums, chunk squares, the W2 image (16-byte aligned in a 16-byte aligned buffer)
+int ppo_grad_floats(void) { return W2IMG_OFF + W2IMG_FLOATS; }
 int ppo_meter_floats(int n_envs, int horizon) {
   return horizon * 4 + horizon * ((n_envs + kStoreTB - 1) / kStoreTB) * 4;
 }
