@@ -979,6 +979,11 @@ int ppo_dp_alloc(void **dptr, void *ipc_handle);
    payload arrived wrong or stale.  Afterwards the ranks agree, reset *dp->err and set *dp->clock to
    key0 + rounds - 1 (the flags' last key), or fall back to collectives. */
 int ppo_dp_selftest(const ppo_dp_t *dp, unsigned key0, int rounds, int timeout_ms, void *stream);
+/* self-test of the library's cross-lane folds (csrc/usv_device.h): wave b of n_waves folds in[64 b .. 64 b + 63]
+   with the DPP / lane-swap forms the kernels use (out_new) and with the shuffle forms (out_shfl), and stores every
+   lane's result: 6 rows of n_waves * 64 floats each -- the 64-lane sum, max, min, the sums over aligned 16- and
+   8-lane groups (partners 1, 2, 4, 8 in that order) and lane i + lane i ^ 32.  The two are equal bit for bit. */
+int usv_wave_fold_selftest(const float *in, int n_waves, float *out_new, float *out_shfl, void *stream);
 /* map another rank's receive buffer (hipIpcOpenMemHandle, lazy peer access) / unmap / free our own */
 int ppo_dp_open(const void *ipc_handle, void **dptr);
 int ppo_dp_close(void *dptr);

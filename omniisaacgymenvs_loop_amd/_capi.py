@@ -102,6 +102,7 @@ def _declare(lib):
         "ppo_dp_close": [P],
         "ppo_dp_free": [P],
         "ppo_dp_selftest": [P, ctypes.c_uint, I, I, P],
+        "usv_wave_fold_selftest": [P, I, P, P, P],
         "ppo_partials_floats": [I],
         "ppo_grad_floats": [],
         "ppo_obs_rms_epoch": [P, P, I, P, P, P],

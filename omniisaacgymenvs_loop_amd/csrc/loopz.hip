@@ -189,11 +189,7 @@ __device__ void tile_forward(int obs_dim, int nout, NetSmem &s) {
       a0 = fmaf(s.w3[k], hv, a0);
       a1 = fmaf(s.w3[NH + k], hv, a1);
     }
-#pragma unroll
-    for (int mm = 1; mm < 8; mm <<= 1) {
-      a0 += __shfl_xor(a0, mm, 64);
-      a1 += __shfl_xor(a1, mm, 64);
-    }
+    a0 = group_sum_up<8>(a0); a1 = group_sum_up<8>(a1);   // every lane active
     if (part == 0) {
       s.out[r * NA] = a0 + s.b3[0];
       if (nout > 1) s.out[r * NA + 1] = a1 + s.b3[1];

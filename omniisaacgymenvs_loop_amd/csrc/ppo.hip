@@ -296,12 +296,7 @@ __device__ __forceinline__ void block_heads(S &s) {
       a1 = fmaf(s.tail[T_WMU + NH + k], hv, a1);
       av = fmaf(s.tail[T_WV + k], hv, av);
     }
-#pragma unroll
-    for (int m = 1; m < 8; m <<= 1) {
-      a0 += __shfl_xor(a0, m, 64);
-      a1 += __shfl_xor(a1, m, 64);
-      av += __shfl_xor(av, m, 64);
-    }
+    a0 = group_sum_up<8>(a0); a1 = group_sum_up<8>(a1); av = group_sum_up<8>(av);   // every lane active
     if (part == 0) {
       s.out[r * 4 + 0] = a0 + s.tail[T_BMU];
       s.out[r * 4 + 1] = a1 + s.tail[T_BMU + 1];
@@ -409,12 +404,7 @@ __device__ __forceinline__ void block_forward_rw(const RegW &wr, PolSmem &s, Pol
       a1 = fmaf(wr.hm1[kk], hv, a1);
       av = fmaf(wr.hv[kk], hv, av);
     }
-#pragma unroll
-    for (int m = 1; m < 8; m <<= 1) {
-      a0 += __shfl_xor(a0, m, 64);
-      a1 += __shfl_xor(a1, m, 64);
-      av += __shfl_xor(av, m, 64);
-    }
+    a0 = group_sum_up<8>(a0); a1 = group_sum_up<8>(a1); av = group_sum_up<8>(av);   // every lane active
     if (part == 0) {
       s.out[r * 4 + 0] = a0 + s.tail[T_BMU];
       s.out[r * 4 + 1] = a1 + s.tail[T_BMU + 1];
@@ -1571,12 +1561,7 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
       a1 = fmaf(s.tail[T_WMU + NH + k], hv, a1);
       av = fmaf(s.tail[T_WV + k], hv, av);
     }
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) {
-      a0 += __shfl_xor(a0, m, 64);
-      a1 += __shfl_xor(a1, m, 64);
-      av += __shfl_xor(av, m, 64);
-    }
+    a0 = group_sum_up<16>(a0); a1 = group_sum_up<16>(a1); av = group_sum_up<16>(av);   // every lane active
     if (part == 0) {
       s.out[r * 4 + 0] = a0 + s.tail[T_BMU];
       s.out[r * 4 + 1] = a1 + s.tail[T_BMU + 1];
@@ -1588,6 +1573,10 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
   // ---- per-row losses and output gradients (lane = row < RB): wave 0 the actor side (ratio, clipped
   // surrogate, dnlp, dmu, dlogstd), wave 1 in parallel the critic loss and dv, wave 2 the bound, entropy and KL
   // terms and the mu / sigma write-back (the same per-row arithmetic and lane sums as one wave doing all) ----
+  // The loss sums (la, gs0, gs1 | lc | le, lb, lkl) feed partial stores only, not s.g or dz2: each owning wave keeps
+  // its per-row terms in ls_a / ls_b / ls_c and folds and stores them behind the dz2 barrier (at the head of dh1), so
+  // no wave waits at the barrier that releases dz2 for sums the backward does not need
+  float ls_a = 0.f, ls_b = 0.f, ls_c = 0.f;
   if (tid < 192) {
     const int r = lane;
     const bool rowok = r < RB;
@@ -1603,7 +1592,6 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
     const float bh0 = fmaxf(mu0 - 1.1f, 0.f), bl0 = fminf(mu0 + 1.1f, 0.f);
     const float bh1 = fmaxf(mu1 - 1.1f, 0.f), bl1 = fminf(mu1 + 1.1f, 0.f);
     if (w == 0) {
-      float la = 0.f, gs0 = 0.f, gs1 = 0.f;
       if (rowok) {
         const float z0 = (ri.act0 - mu0) / sg0, z1 = (ri.act1 - mu1) / sg1;
         const float nlp = 0.5f * (z0 * z0 + z1 * z1) + kLog2Pi + (ls0 + ls1);
@@ -1624,22 +1612,16 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
         const float dmu1 = dnlp * (-z1 / sg1) + bc * 2.f * (bh1 + bl1);
         // d nlp / d logstd = 1 - z^2; - entropy_coef * mean(entropy): d entropy / d logstd = 1 per row
         const float dent = -c.entropy_coef * invB;
-        gs0 = dnlp * (1.f - z0 * z0) + dent;
-        gs1 = dnlp * (1.f - z1 * z1) + dent;
-        la = a_loss;
+        ls_b = dnlp * (1.f - z0 * z0) + dent;   // gs0
+        ls_c = dnlp * (1.f - z1 * z1) + dent;   // gs1
+        ls_a = a_loss;                          // la
         s.g[r * 4 + 0] = dmu0;
         s.g[r * 4 + 1] = dmu1;
         s.g[r * 4 + 3] = dnlp;
       }
-      la = wave_sum(la); gs0 = wave_sum(gs0); gs1 = wave_sum(gs1);
-      if (lane == 0) {
-        part_st(P_LOSS + 0, la);
-        part_st(S_SIG, gs0); part_st(S_SIG + 1, gs1);
-      }
     } else if (w == 2) {
       // the KL, entropy and bound terms and the mu / sigma write-back on a wave of their own: they feed the
       // loss sums and the adaptive LR only, not this minibatch's backward
-      float le = 0.f, lb = 0.f, lkl = 0.f;
       if (rowok) {
         const float b_loss = (bl0 * bl0 + bh0 * bh0) + (bl1 * bl1 + bh1 * bh1);
         const float ent = (0.5f + 0.5f * logf(USV_2PI_F) + ls0) + (0.5f + 0.5f * logf(USV_2PI_F) + ls1);
@@ -1649,14 +1631,9 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
         const float kl1 = logf(os1 / sg1 + 1e-5f) + (sg1 * sg1 + (om1 - mu1) * (om1 - mu1)) / (2.0f * (os1 * os1 + 1e-5f)) - 0.5f;
         e_mu[row * 2] = mu0; e_mu[row * 2 + 1] = mu1;
         e_sigma[row * 2] = sg0; e_sigma[row * 2 + 1] = sg1;
-        le = ent; lb = b_loss; lkl = kl0 + kl1;
-      }
-      le = wave_sum(le); lb = wave_sum(lb); lkl = wave_sum(lkl);
-      if (lane == 0) {
-        part_st(P_LOSS + 2, le); part_st(P_LOSS + 3, lb); part_st(P_LOSS + 4, lkl);
+        ls_a = ent; ls_b = b_loss; ls_c = kl0 + kl1;   // le, lb, lkl
       }
     } else {
-      float lc = 0.f;
       if (rowok) {
         // critic_loss (common_losses.py:10-19)
         const float vo = ri.val, R = ri.ret;
@@ -1675,11 +1652,9 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
           dv = 2.f * (v - R);
         }
         dv *= 0.5f * c.critic_coef * invB;
-        lc = c_loss;
+        ls_a = c_loss;   // lc
         s.g[r * 4 + 2] = dv;
       }
-      lc = wave_sum(lc);
-      if (lane == 0) part_st(P_LOSS + 1, lc);
     }
   }
   __syncthreads();
@@ -1714,6 +1689,23 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
   // (a barrier that runs dh1 alone first measured +1.1 us per minibatch: the stores then meet the write bandwidth) ----
   f32x16 dh = {};
   if (w < 4) {
+    // the deferred loss sums of waves 0-2 (every lane active: w is wave-uniform), the same folds into the same slots;
+    // VALU only, in the shadow of the SIMD's other wave (w + 4), which starts dW2 on the matrix core
+    if (w == 0) {
+      const float la = wave_sum(ls_a), gs0 = wave_sum(ls_b), gs1 = wave_sum(ls_c);
+      if (lane == 0) {
+        part_st(P_LOSS + 0, la);
+        part_st(S_SIG, gs0); part_st(S_SIG + 1, gs1);
+      }
+    } else if (w == 2) {
+      const float le = wave_sum(ls_a), lb = wave_sum(ls_b), lkl = wave_sum(ls_c);
+      if (lane == 0) {
+        part_st(P_LOSS + 2, le); part_st(P_LOSS + 3, lb); part_st(P_LOSS + 4, lkl);
+      }
+    } else if (w == 1) {
+      const float lc = wave_sum(ls_a);
+      if (lane == 0) part_st(P_LOSS + 1, lc);
+    }
     if constexpr (kBf) {
 #pragma unroll
       for (int st = 0; st < NH / 16; ++st) {
@@ -1761,8 +1753,8 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
       sb += dz1[q];
       sc = fmaf(dz1[q], s.x[crow(q, h) * XG + NIN - 1], sc);
     }
-    sb += __shfl_xor(sb, 32, 64);   // rows of h = 0 + rows of h = 1 (the same sum in both lanes)
-    sc += __shfl_xor(sc, 32, 64);
+    sb = half_pair_sum(sb);   // rows of h = 0 + rows of h = 1 (the same sum in both lanes)
+    sc = half_pair_sum(sc);
 #pragma unroll
     for (int a = 0; a < 4; ++a)
       part_st.x4(acc_slot(S_W1, cb, a, lane), acc[4 * a], acc[4 * a + 1], acc[4 * a + 2], acc[4 * a + 3]);
@@ -2228,9 +2220,37 @@ __global__ __launch_bounds__(AP_TB) void k_apply(ppo_cfg_t c, AdamBanks a, const
   if (blockIdx.x == 0 && tid == 0) opt_store(c, nx, opt_out, total_norm, kl, kl_out);
 }
 
+// The fold self-test (usv_wave_fold_selftest): wave b folds in[64 b .. 64 b + 63] with the DPP / permlane forms
+// (out_new) and with the shuffle forms (out_shfl), every lane's result stored: rows of n_waves * 64 floats in the
+// order sum, max, min (64 lanes), 16-lane and 8-lane ascending sums, the cross-half pair sum.
+__global__ __launch_bounds__(64) void k_wave_fold_selftest(const float *__restrict__ in, float *__restrict__ out_new,
+                                                           float *__restrict__ out_shfl) {
+  const size_t q = (size_t)blockIdx.x * 64 + threadIdx.x, n = (size_t)gridDim.x * 64;
+  const float v = in[q];
+  out_new[q] = wave_sum(v);
+  out_new[n + q] = wave_max(v);
+  out_new[2 * n + q] = wave_min(v);
+  out_new[3 * n + q] = group_sum_up<16>(v);
+  out_new[4 * n + q] = group_sum_up<8>(v);
+  out_new[5 * n + q] = half_pair_sum(v);
+  out_shfl[q] = wave_sum_shfl(v);
+  out_shfl[n + q] = wave_max_shfl(v);
+  out_shfl[2 * n + q] = wave_min_shfl(v);
+  out_shfl[3 * n + q] = group_sum_up_shfl<16>(v);
+  out_shfl[4 * n + q] = group_sum_up_shfl<8>(v);
+  out_shfl[5 * n + q] = v + __shfl_xor(v, 32, 64);
+}
+
 }  // namespace
 
 extern "C" {
+
+int usv_wave_fold_selftest(const float *in, int n_waves, float *out_new, float *out_shfl, void *stream) {
+  if (!in || !out_new || !out_shfl || n_waves < 1 || n_waves > 65535) return 1;
+  hipLaunchKernelGGL(k_wave_fold_selftest, dim3(n_waves), dim3(64), 0, (hipStream_t)stream, in, out_new, out_shfl);
+  USV_CHECK_LAUNCH();
+  return 0;
+}
 
 int ppo_policy_step(const ppo_cfg_t *cfg, const float *params, const double *obs_rms, const double *val_rms,
                     const float *obs, int t, float *exp_obs, float *exp_act, float *exp_nlp, float *exp_val,

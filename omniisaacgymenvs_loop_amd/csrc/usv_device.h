@@ -345,19 +345,102 @@ __device__ __forceinline__ float2 place_obstacles(const usv_cfg_t &c, int ee, fl
 }
 
 
-__device__ __forceinline__ float wave_sum(float v) {
+// ---------------------------------------------------------------------------
+// Cross-lane folds without LDS permutes.  __shfl_xor is a ds_bpermute_b32: an LDS-pipe round trip and an lgkmcnt
+// wait per level.  The forms below take the SAME partner (lane ^ m) at every level in the SAME level order, with
+// VALU data movement only, so every lane ends with the bits the shuffle form gives (fp32 add / min / max of the
+// same two operands commute):
+//   m = 1, 2   DPP quad_perm [1,0,3,2] / [2,3,0,1]
+//   m = 4      two DPP moves: row_shl:4 into banks 0 and 2 (lanes with bit 2 clear read lane + 4), row_shr:4 into
+//              banks 1 and 3 (no single DPP control is xor 4; row_half_mirror pairs other lanes)
+//   m = 8      DPP row_ror:8 (a rotation by half a 16-lane row is xor 8; row_mirror pairs other lanes)
+//   m = 16, 32 v_permlane16_swap / v_permlane32_swap of two copies of v: the first result holds the value of the
+//              lane with bit m clear, the second that of the lane with bit m set, in both lanes of a pair
+// ALL 64 LANES MUST BE ACTIVE at the call (wave-uniform control flow): a DPP read of a disabled lane is not the
+// shuffle's.  Every call site of the library is wave-uniform (conditions on the wave index, or branches closed
+// before the fold); a divergent one keeps the *_shfl form.
+// ---------------------------------------------------------------------------
+// (bound_ctrl with every bank enabled: no lane of these controls reads out of its row, so it changes no value and
+// lets the compiler fuse the move into the add / max / min that uses it)
+template <int kCtrl, int kBankMask>
+__device__ __forceinline__ float dpp_mov(float old, float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v),
+                                                               kCtrl, 0xF, kBankMask, kBankMask == 0xF));
+}
+// the value of lane ^ kXor, kXor in {1, 2, 4, 8}
+template <int kXor>
+__device__ __forceinline__ float lane_xor_dpp(float v) {
+  static_assert(kXor == 1 || kXor == 2 || kXor == 4 || kXor == 8, "in-row partners only");
+  if constexpr (kXor == 1) return dpp_mov<0xB1, 0xF>(v, v);         // quad_perm:[1,0,3,2]
+  else if constexpr (kXor == 2) return dpp_mov<0x4E, 0xF>(v, v);    // quad_perm:[2,3,0,1]
+  else if constexpr (kXor == 8) return dpp_mov<0x128, 0xF>(v, v);   // row_ror:8
+  else return dpp_mov<0x114, 0xA>(dpp_mov<0x104, 0x5>(v, v), v);    // row_shl:4 bank_mask:0x5, row_shr:4 bank_mask:0xA
+}
+struct FoldAdd { __device__ __forceinline__ float operator()(float a, float b) const { return a + b; } };
+struct FoldMax { __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); } };
+struct FoldMin { __device__ __forceinline__ float operator()(float a, float b) const { return fminf(a, b); } };
+// one level of the 64-lane butterfly across rows, kXor in {16, 32}
+template <int kXor, class Op>
+__device__ __forceinline__ float fold_rows(float v, Op op) {
+  static_assert(kXor == 16 || kXor == 32, "row partners only");
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  if constexpr (kXor == 32) {
+    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    return op(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
+  } else {
+    const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    return op(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
+  }
+}
+// the whole wave's fold, partners 32, 16, 8, 4, 2, 1 in that order: the result in every lane
+template <class Op>
+__device__ __forceinline__ float wave_fold(float v, Op op) {
+  v = fold_rows<32>(v, op);
+  v = fold_rows<16>(v, op);
+  v = op(v, lane_xor_dpp<8>(v));
+  v = op(v, lane_xor_dpp<4>(v));
+  v = op(v, lane_xor_dpp<2>(v));
+  v = op(v, lane_xor_dpp<1>(v));
+  return v;
+}
+__device__ __forceinline__ float wave_sum(float v) { return wave_fold(v, FoldAdd{}); }
+__device__ __forceinline__ float wave_max(float v) { return wave_fold(v, FoldMax{}); }
+__device__ __forceinline__ float wave_min(float v) { return wave_fold(v, FoldMin{}); }
+// the sum over each aligned group of kW lanes (kW = 8 or 16), partners 1, 2, 4 (, 8) in that order -- the heads'
+// `for (m = 1; m < kW; m <<= 1) a += __shfl_xor(a, m)`: the result in every lane of the group
+template <int kW>
+__device__ __forceinline__ float group_sum_up(float v) {
+  static_assert(kW == 8 || kW == 16, "groups inside a 16-lane row");
+  v += lane_xor_dpp<1>(v);
+  v += lane_xor_dpp<2>(v);
+  v += lane_xor_dpp<4>(v);
+  if constexpr (kW == 16) v += lane_xor_dpp<8>(v);
+  return v;
+}
+// lanes i and i ^ 32 both get v[i] + v[i ^ 32]
+__device__ __forceinline__ float half_pair_sum(float v) { return fold_rows<32>(v, FoldAdd{}); }
+
+// The shuffle forms of the folds above (one ds_bpermute_b32 per level): the reference of the fold self-test
+// (usv_wave_fold_selftest), and the form for a call site whose lanes are not all active.
+__device__ __forceinline__ float wave_sum_shfl(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
-__device__ __forceinline__ float wave_max(float v) {
+__device__ __forceinline__ float wave_max_shfl(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
   return v;
 }
-__device__ __forceinline__ float wave_min(float v) {
+__device__ __forceinline__ float wave_min_shfl(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
+  return v;
+}
+template <int kW>
+__device__ __forceinline__ float group_sum_up_shfl(float v) {
+#pragma unroll
+  for (int m = 1; m < kW; m <<= 1) v += __shfl_xor(v, m, 64);
   return v;
 }
 

@@ -729,13 +729,7 @@ __global__ __launch_bounds__(256) void k_field_batch(usv_cfg_t c, usv_bufs_t b) 
     }
   }
   // wave maxima over the lanes (max is exact in any order)
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    gfin = fmaxf(gfin, __shfl_xor(gfin, off, 64));
-    jf = fmaxf(jf, __shfl_xor(jf, off, 64));
-    jr = fmaxf(jr, __shfl_xor(jr, off, 64));
-    ins = fmaxf(ins, __shfl_xor(ins, off, 64));
-  }
+  gfin = wave_max(gfin); jf = wave_max(jf); jr = wave_max(jr); ins = wave_max(ins);   // every lane active
   if (lane == 0) { wred[wid][0] = gfin; wred[wid][1] = jf; wred[wid][2] = jr; wred[wid][3] = ins; }
   __syncthreads();
   if (tid == 0) {
