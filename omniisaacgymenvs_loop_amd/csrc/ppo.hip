@@ -821,17 +821,32 @@ __global__ __launch_bounds__(FIN_TB) void k_prepare_finalize(ppo_cfg_t c, double
   work[5] = sqrt(va > 0 ? va : 0.0);
 }
 
+// x - mean for the normalisations of k_prepare_apply.  The reference's fp32 form x - (float)mean carries the
+// mean's fp32 rounding, up to 2^-24 |mean|, into a difference that is then divided by the spread sd: an error of
+// 2^-24 |mean| / sd in the normalised value.  Up to |mean| = 64 sd that is below 4e-6 and the fp32 form stays,
+// bit for bit.  Beyond it -- denormalised values and returns late in training, 1e3 +- 1e-2, where it reaches 3e-3
+// -- the difference is taken in double (tests/test_ppo_prepare_edges_gpu.py, the large-mean family).  mean and sd
+// are the batch's scalars, so the choice is uniform over the grid.
+constexpr float kWideMeanRatio = 64.0f;
+__device__ __forceinline__ float diff_from_mean(float x, double mean, float sd) {
+  return fabs(mean) > (double)(kWideMeanRatio * sd) ? (float)((double)x - mean) : x - (float)mean;
+}
+__device__ __forceinline__ float rms_norm_wide(float x, double mean, double var, float eps) {
+  const float sd = sqrtf((float)var + eps);
+  return clampt(diff_from_mean(x, mean, sd) / sd, -5.0f, 5.0f);
+}
+
 __global__ void k_prepare_apply(ppo_cfg_t c, const double *work, float *val, float *ret, float *adv) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t B = (size_t)c.n_envs * c.horizon;
   if (i >= B) return;
   if (c.normalize_value) {
-    val[i] = rms_norm(val[i], work[0], work[1], c.rms_eps);
-    ret[i] = rms_norm(ret[i], work[2], work[3], c.rms_eps);
+    val[i] = rms_norm_wide(val[i], work[0], work[1], c.rms_eps);
+    ret[i] = rms_norm_wide(ret[i], work[2], work[3], c.rms_eps);
   }
   if (c.normalize_advantage) {
-    // (adv - adv.mean()) / (adv.std() + 1e-8)  (:1287)
-    adv[i] = (adv[i] - (float)work[4]) / ((float)work[5] + 1e-8f);
+    // (adv - adv.mean()) / (adv.std() + 1e-8)  (:1287); the difference as in rms_norm_wide
+    adv[i] = diff_from_mean(adv[i], work[4], (float)work[5]) / ((float)work[5] + 1e-8f);
   }
 }
 
