@@ -21,6 +21,7 @@
 #include "usv_layout_gen.h"
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstddef>
 
@@ -741,6 +742,224 @@ __device__ __forceinline__ StepCfg step_cfg_reload() {
 #endif
 }
 
+// ------------------------------------------------------------------------
+// What every control step does, whatever the task: k_env_step (CaptureXY) and k_env_step_task call these; each
+// kernel keeps its own loads, stores and config reload points and hands in the c / K of its current reload.
+// ------------------------------------------------------------------------
+// VecEnvRLGames.step clamp (vec_env_rlgames.py:136-140) + pre_physics_step (USV_Virtual.py:1050-1099) + the index
+// of DynamicsFirstOrder.get_cmd_interpolated (ThrusterDynamics.py:179-219); the caller reads its LUT copy
+struct ActionMap {
+  float cmd0, cmd1;             // the clamped actions
+  float prev_cmd0, prev_cmd1;   // what the observation shows as the previous command (0 at a reset)
+  float t0, t1, unit0, unit1;   // biased, noised, clamped command and its thrust unit in [0, 1]
+  int i0, i1;                   // LUT rows (a reset env commands 0 thrust)
+};
+__device__ __forceinline__ ActionMap action_map(const usv_cfg_t &c, const StepK &K, float2 a2, bool was_reset,
+                                                float bias, const float *u) {
+  ActionMap a;
+  a.cmd0 = clampt(a2.x, -c.clip_actions, c.clip_actions);
+  a.cmd1 = clampt(a2.y, -c.clip_actions, c.clip_actions);
+  a.prev_cmd0 = was_reset ? 0.f : a.cmd0;
+  a.prev_cmd1 = was_reset ? 0.f : a.cmd1;
+  float t0 = a.cmd0, t1 = a.cmd1;
+  if (bias != 0.f) { t0 = t0 + bias; t1 = t1 + bias; }
+  if (c.act_noise_on) {
+    t0 = t0 + (u[SU_ACT] * K.act_rng + c.act_noise_min);
+    t1 = t1 + (u[SU_ACT + 1] * K.act_rng + c.act_noise_min);
+  }
+  a.t0 = clampt(t0, -1.f, 1.f);
+  a.t1 = clampt(t1, -1.f, 1.f);
+  const float unit0 = c.affine_thrust ? 0.5f * (a.t0 + 1.0f) : clampt(a.t0, 0.f, 1.f);
+  const float unit1 = c.affine_thrust ? 0.5f * (a.t1 + 1.0f) : clampt(a.t1, 0.f, 1.f);
+  a.unit0 = clampt(unit0, 0.f, 1.f);
+  a.unit1 = clampt(unit1, 0.f, 1.f);
+  const float uu0 = was_reset ? 0.f : a.unit0, uu1 = was_reset ? 0.f : a.unit1;
+  const int i0 = (int)rintf(((uu0 + 1.0f) / 2.0f) * (float)(USV_LUT_N - 1));
+  const int i1 = (int)rintf(((uu1 + 1.0f) / 2.0f) * (float)(USV_LUT_N - 1));
+  a.i0 = min(max(i0, 0), USV_LUT_N - 1);
+  a.i1 = min(max(i1, 0), USV_LUT_N - 1);
+  return a;
+}
+
+// damping per body axis (Hydrodynamics.py:239-243): (linear + quadratic |v|) scaling_damping [k_drag]; the drag
+// force is -D v.  kd is the env's k_drag (read only with use_drag_scale)
+struct Damping {
+  float lin0, lin1, lin2, qd0, qd1, qd2;
+};
+struct Drag3 {
+  float D0, D1, D2;
+};
+__device__ __forceinline__ Drag3 drag_coeffs(const usv_cfg_t &c, const Damping &d, float kd, float ub, float vb,
+                                             float rb) {
+  Drag3 D{d.lin0 + d.qd0 * fabsf(ub), d.lin1 + d.qd1 * fabsf(vb), d.lin2 + d.qd2 * fabsf(rb)};
+  D.D0 = D.D0 * c.scaling_damping; D.D1 = D.D1 * c.scaling_damping; D.D2 = D.D2 * c.scaling_damping;
+  if (c.use_drag_scale) { D.D0 = D.D0 * kd; D.D1 = D.D1 * kd; D.D2 = D.D2 * kd; }
+  return D;
+}
+
+// ---- the substeps: thruster lag, planar forces, semi-implicit Euler.  The integrator is this build's own (it
+// replaces PhysX): accelerations divide by m and Izz through their reciprocals with one correction step
+// (div_rn == the IEEE quotient for quotients in [2^-90, 2^120]) ----
+struct BodyState {
+  float px, py, yaw, vx, vy, wz, fl, fr;
+};
+struct SubstepIn {
+  float lut0, lut1;                      // the thruster LUT's entries at ActionMap::i0 / i1
+  float m, k_iz, k_drag, thr_l, thr_r, comy;
+  Damping damp;                          // the env's (drag DR) or the config's
+  float dp[USV_NDIST], orgx, orgy;       // disturbance parameters (drawn at reset), env origin: read with dist only
+  bool stl;                              // a reset env's first substep sees the pre-reset inputs usv_reset kept
+  float st_ub, st_vb, st_rb, st_px, st_py;   // (st_px / st_py with dist only)
+};
+// dist: any disturbance term or the water current on (a compile-time constant in k_env_step, uniform in the
+// task kernel)
+__device__ __forceinline__ void integrate_substeps(const usv_cfg_t &c, const SubstepIn &in, bool dist, BodyState &s) {
+  float tgt0 = in.lut0, tgt1 = in.lut1;
+  if (c.use_thr_mult) { tgt0 = tgt0 * in.thr_l; tgt1 = tgt1 * in.thr_r; }
+  const float m = in.m, izz = c.izz0 * in.k_iz;
+  const float inv_m = 1.0f / m, inv_izz = 1.0f / izz;
+  const float kd = c.use_drag_scale ? in.k_drag : 1.0f;
+  const float al = c.thr_alpha, oma = 1.0f - c.thr_alpha;
+  const float dt = c.dt;
+  const float arm_l = -(c.thr_y - in.comy), arm_r = c.thr_y + in.comy;
+  const float *dp = in.dp;
+  float px = s.px, py = s.py, yaw = s.yaw, vx = s.vx, vy = s.vy, wz = s.wz, fl = s.fl, fr = s.fr;
+  for (int i = 0; i < c.substeps; ++i) {
+    fl = fl * al + oma * tgt0;                      // ThrusterDynamics.py:133-136
+    fr = fr * al + oma * tgt1;
+    // the attitude the reference reads back: R = quaternion_to_matrix(q(yaw)) (usv_quat_rot)
+    const QuatRot qr = usv_quat_rot(yaw);
+    const float sy_ = qr.S, cy_ = qr.C;
+    float ub = cy_ * vx + sy_ * vy;                 // R^T v (Utils.py:10-14, Hydrodynamics.py:209-217)
+    float vb = -sy_ * vx + cy_ * vy;
+    float rb = wz;
+    float hpx = px, hpy = py;
+    if (dist && c.current_on) {                     // relative to the water (Hydrodynamics.py:224-237)
+      ub = ub - (cy_ * c.flow_vel[0] + sy_ * c.flow_vel[1]);
+      vb = vb - (-sy_ * c.flow_vel[0] + cy_ * c.flow_vel[1]);
+    }
+    if (i == 0) {                                   // the cached pre-reset root state
+      ub = in.stl ? in.st_ub : ub;
+      vb = in.stl ? in.st_vb : vb;
+      rb = in.stl ? in.st_rb : rb;
+      hpx = in.stl ? in.st_px : hpx;
+      hpy = in.stl ? in.st_py : hpy;
+    }
+    float dfx = 0.f, dfy = 0.f, dtz = 0.f;
+    if (dist) {
+      // get_disturbance_forces / get_torque_disturbance at root_pos (USV_disturbances.py:386-410,510-530)
+      const float wx = hpx + in.orgx, wy = hpy + in.orgy;
+      dfx = dp[DI_FCX];
+      dfy = dp[DI_FCY];
+      dtz = dp[DI_TC];
+      if (c.fsin_on) {
+        dfx = dfx + usv_sin_cr(wx * dp[DI_FXF] + dp[DI_FXS]) * dp[DI_FAMP];
+        dfy = dfy + usv_sin_cr(wy * dp[DI_FYF] + dp[DI_FYS]) * dp[DI_FAMP];
+      }
+      if (c.tsin_on) dtz = dtz + usv_sin_cr((wx + wy) * dp[DI_TF] + dp[DI_TS]) * dp[DI_TAMP];
+    }
+    const Drag3 D = drag_coeffs(c, in.damp, kd, ub, vb, rb);
+    // base force = disturbance + drag (+ hydrostatics, 0 in the plane), thrusters (USV_Virtual.py:1118-1132)
+    const float X = dist ? fl + fr + (dfx + (-D.D0 * ub)) : fl + fr + (-D.D0 * ub);   // Hydrodynamics.py:243
+    const float Y = dist ? dfy + (-D.D1 * vb) : -D.D1 * vb;
+    const float N = dist ? arm_l * fl + arm_r * fr + (dtz + (-D.D2 * rb)) : arm_l * fl + arm_r * fr + (-D.D2 * rb);
+    const float ax = div_rn(cy_ * X - sy_ * Y, m, inv_m);
+    const float ay = div_rn(sy_ * X + cy_ * Y, m, inv_m);
+    const float aw = div_rn(N, izz, inv_izz);
+    vx = vx + ax * dt;
+    vy = vy + ay * dt;
+    wz = wz + aw * dt;
+    px = px + vx * dt;
+    py = py + vy * dt;
+    float yw = yaw + wz * dt;
+    if (yw > USV_PI_F) yw -= USV_2PI_F;
+    else if (yw <= -USV_PI_F) yw += USV_2PI_F;
+    yaw = yw;
+  }
+  s = BodyState{px, py, yaw, vx, vy, wz, fl, fr};
+}
+
+// ---- update_state's noise (USV_Virtual.py:771-813).  The position stands alone: k_env_step issues the
+// potential's texel loads as soon as it exists ----
+__device__ __forceinline__ float2 observed_position(const usv_cfg_t &c, const StepK &K, const float *u, float px,
+                                                    float py) {
+  float pxn = px, pyn = py;
+  if (c.pos_noise_on) {
+    pxn = pxn + (u[SU_PX] * K.pos_rng + c.pos_noise_min);
+    pyn = pyn + (u[SU_PX + 1] * K.pos_rng + c.pos_noise_min);
+  }
+  return make_float2(pxn, pyn);
+}
+struct ObservedMotion {
+  float vxn, vyn, wzn;
+  float yawn, hs, hc;   // the noisy heading, its sine and cosine
+};
+__device__ __forceinline__ ObservedMotion observed_motion(const usv_cfg_t &c, const StepK &K, const float *u,
+                                                          const BodyState &s) {
+  ObservedMotion o{s.vx, s.vy, s.wz, 0.f, 0.f, 0.f};
+  if (c.vel_noise_on) {
+    o.vxn = o.vxn + (u[SU_VX] * K.vel_rng + c.vel_noise_min);
+    o.vyn = o.vyn + (u[SU_VY] * K.vel_rng + c.vel_noise_min);
+    o.wzn = o.wzn + (u[SU_WZ] * K.vel_rng + c.vel_noise_min);
+  }
+  // update_state's heading: atan2 of the read-back quaternion (USV_Virtual.py:776-786), then its noise
+  o.yawn = usv_heading(usv_quat_rot(s.yaw));
+  if (c.head_noise_on) o.yawn = o.yawn + (u[SU_HEAD] * K.head_rng + c.head_noise_min);
+  usv_sincos(o.yawn, &o.hs, &o.hc);
+  return o;
+}
+// observation columns 0-2: the velocity in the body or the world frame (static_obs.py:193-299, USV_core.py:55-121)
+template <class Put>
+__device__ __forceinline__ void put_velocity_columns(const usv_cfg_t &c, const ObservedMotion &o, Put put) {
+  if (c.obs_local) {
+    put(0, o.hc * o.vxn + o.hs * o.vyn);
+    put(1, -o.hs * o.vxn + o.hc * o.vyn);
+  } else {
+    put(0, o.vxn);
+    put(1, o.vyn);
+  }
+  put(2, o.wzn);
+}
+
+// ---- Penalties.compute_penalty (USV_task_rewards.py:440-523) without its action-variation term ----
+struct StepPenalties {
+  float p_ang, p_angv, p_en;   // the terms with an episode sum
+  float sum;                   // ((p_lin + p_ang) + p_angv) + p_en
+};
+__device__ __forceinline__ StepPenalties step_penalties(const usv_cfg_t &c, const ActionMap &a, const ObservedMotion &o,
+                                                        bool pen_valid, float prev_wz_mem) {
+  const float pact0 = c.pen_use_u ? a.unit0 : a.cmd0, pact1 = c.pen_use_u ? a.unit1 : a.cmd1;
+  float p_lin = 0.f, p_ang = 0.f, p_angv = 0.f, p_en = 0.f;
+  if (c.pen_lin_kind == PEN_NORM) p_lin = -tnorm2(o.vxn, o.vyn) * c.pen_lin_k + c.pen_lin_c;
+  if (c.pen_ang_kind) p_ang = pen_scalar(c.pen_ang_kind, c.pen_ang_k, c.pen_ang_x0, c.pen_ang_c, o.wzn);
+  if (c.pen_angv_kind) {
+    const float prev_w = pen_valid ? prev_wz_mem : o.wzn;
+    p_angv = pen_scalar(c.pen_angv_kind, c.pen_angv_k, c.pen_angv_x0, c.pen_angv_c, o.wzn - prev_w);
+  }
+  if (c.pen_en_kind == PEN_SUM) p_en = -(pact0 + pact1) * c.pen_en_k + c.pen_en_c;
+  else if (c.pen_en_kind == PEN_SUMSQ) p_en = -(pact0 * pact0 + pact1 * pact1) * c.pen_en_k + c.pen_en_c;
+  return StepPenalties{p_ang, p_angv, p_en, ((p_lin + p_ang) + p_angv) + p_en};
+}
+
+// the NaN probe's bits for the clamped actions and the observed state (the reward's and the obs row's are the caller's)
+__device__ __forceinline__ uint32_t nan_bits_actions_state(const ActionMap &a, float2 pn, const ObservedMotion &o) {
+  return ((nonfinite(a.cmd0) | nonfinite(a.cmd1)) ? USV_NAN_ACTIONS : 0u) |
+         ((nonfinite(pn.x) | nonfinite(pn.y) | nonfinite(o.yawn) | nonfinite(o.vxn) | nonfinite(o.vyn) |
+           nonfinite(o.wzn)) ? USV_NAN_STATE : 0u);
+}
+
+// the step's addends to the state statistics every task keeps (USV_Virtual.py:584-601)
+constexpr int kStateStatKey[6] = {ST_NORMED_LINEAR_VEL, ST_NORMED_ANGULAR_VEL, ST_CMD_NEG_RATE,
+                                  ST_U_MEAN,            ST_U_LOW_RATE,         ST_U_SUM};
+struct StateStats {
+  float v[6];   // kStateStatKey's order
+};
+__device__ __forceinline__ StateStats state_stats(const ActionMap &a, const ObservedMotion &o) {
+  return StateStats{{tnorm2(o.vxn, o.vyn), fabsf(o.wzn), ((float)(a.t0 < 0.f) + (float)(a.t1 < 0.f)) / 2.0f,
+                     (a.unit0 + a.unit1) / 2.0f, ((float)(a.unit0 < 0.05f) + (float)(a.unit1 < 0.05f)) / 2.0f,
+                     a.unit0 + a.unit1}};
+}
+
 template <bool kStats, bool kInj, bool kDist, class Win>
 __global__ __launch_bounds__(kBlock) void k_env_step(StepCfg ck, usv_bufs_t b, Win w,
                                                      const char *__restrict__ wbase, const float *__restrict__ actions,
@@ -795,9 +1014,8 @@ __global__ __launch_bounds__(kBlock) void k_env_step(StepCfg ck, usv_bufs_t b, W
   {
     // ---- every per-env input that does not depend on this step's results is loaded
     // up front, so the HBM latencies overlap each other and the physics ----
-    float px = bld(R, w.px, v4), py = bld(R, w.py, v4), yaw = bld(R, w.yaw, v4);
-    float vx = bld(R, w.vx, v4), vy = bld(R, w.vy, v4), wz = bld(R, w.wz, v4);
-    float fl = bld(R, w.fl, v4), fr = bld(R, w.fr, v4);
+    BodyState s{bld(R, w.px, v4), bld(R, w.py, v4), bld(R, w.yaw, v4), bld(R, w.vx, v4), bld(R, w.vy, v4),
+                bld(R, w.wz, v4), bld(R, w.fl, v4), bld(R, w.fr, v4)};
     const float m = bld(R, w.mass, v4);
     const float k_iz = bld(R, w.k_iz, v4), k_drag = bld(R, w.k_drag, v4);
     const float thr_l = bld(R, w.thr_l, v4), thr_r = bld(R, w.thr_r, v4);
@@ -808,27 +1026,30 @@ __global__ __launch_bounds__(kBlock) void k_env_step(StepCfg ck, usv_bufs_t b, W
     const float l0 = bld(R, w.lin_damp, v4), l1 = bld(R, w.lin_damp + w.n4, v4), l2 = bld(R, w.lin_damp + 2 * w.n4, v4);
     const float q0 = bld(R, w.quad_damp, v4), q1 = bld(R, w.quad_damp + w.n4, v4);
     const float q2 = bld(R, w.quad_damp + 2 * w.n4, v4);
-    const float lin0 = dr ? l0 : c.lin_damp[0], lin1 = dr ? l1 : c.lin_damp[1], lin2 = dr ? l2 : c.lin_damp[2];
-    const float qd0 = dr ? q0 : c.quad_damp[0], qd1 = dr ? q1 : c.quad_damp[1], qd2 = dr ? q2 : c.quad_damp[2];
+    SubstepIn in;
+    in.damp = Damping{dr ? l0 : c.lin_damp[0], dr ? l1 : c.lin_damp[1], dr ? l2 : c.lin_damp[2],
+                      dr ? q0 : c.quad_damp[0], dr ? q1 : c.quad_damp[1], dr ? q2 : c.quad_damp[2]};
     // disturbance parameters (drawn at reset) and the env origin (root_pos is world-frame)
-    float dp[USV_NDIST], orgx = 0.f, orgy = 0.f;
+    in.orgx = 0.f;
+    in.orgy = 0.f;
     if (kDist) {
 #pragma unroll
-      for (int q = 0; q < USV_NDIST; ++q) dp[q] = bld(R, w.dist + (uint32_t)q * w.n4, v4);
+      for (int q = 0; q < USV_NDIST; ++q) in.dp[q] = bld(R, w.dist + (uint32_t)q * w.n4, v4);
       const float ox_ = bld(R, w.env_org, v4), oy_ = bld(R, w.env_org + w.n4, v4);
-      orgx = b.env_org ? ox_ : 0.f;
-      orgy = b.env_org ? oy_ : 0.f;
+      in.orgx = b.env_org ? ox_ : 0.f;
+      in.orgy = b.env_org ? oy_ : 0.f;
     }
     // a reset env's first substep: the pre-reset inputs usv_reset kept; the other lanes
     // read past the window (no memory access, 0)
-    const bool stl = c.stale_root && was_reset;
-    const uint32_t vst = stl ? v4 : kDrop;
-    const float st_ub = bld(R, w.stale + USV_STALE_UB * w.n4, vst), st_vb = bld(R, w.stale + USV_STALE_VB * w.n4, vst);
-    const float st_rb = bld(R, w.stale + USV_STALE_RB * w.n4, vst);
-    float st_px = 0.f, st_py = 0.f;
+    in.stl = c.stale_root && was_reset;
+    const uint32_t vst = in.stl ? v4 : kDrop;
+    in.st_ub = bld(R, w.stale + USV_STALE_UB * w.n4, vst);
+    in.st_vb = bld(R, w.stale + USV_STALE_VB * w.n4, vst);
+    in.st_rb = bld(R, w.stale + USV_STALE_RB * w.n4, vst);
+    in.st_px = in.st_py = 0.f;
     if (kDist) {
-      st_px = bld(R, w.stale + USV_STALE_PX * w.n4, vst);
-      st_py = bld(R, w.stale + USV_STALE_PY * w.n4, vst);
+      in.st_px = bld(R, w.stale + USV_STALE_PX * w.n4, vst);
+      in.st_py = bld(R, w.stale + USV_STALE_PY * w.n4, vst);
     }
     __builtin_amdgcn_sched_barrier(0);   // keep the substep inputs ahead of the loads below
     const int progress0 = bldi(R, w.progress, v4);
@@ -869,29 +1090,7 @@ __global__ __launch_bounds__(kBlock) void k_env_step(StepCfg ck, usv_bufs_t b, W
       if (c.pos_noise_on || c.act_noise_on) philox_u4(seed, (uint32_t)e, step, 1u, u + 4);
       else u[4] = u[5] = u[6] = u[7] = 0.f;
     }
-    // ---- VecEnvRLGames.step clamp (:136-140) + pre_physics_step (:1050-1099) ----
-    const float cmd0 = clampt(a2.x, -c.clip_actions, c.clip_actions);
-    const float cmd1 = clampt(a2.y, -c.clip_actions, c.clip_actions);
-    const float prev_cmd0 = was_reset ? 0.f : cmd0;
-    const float prev_cmd1 = was_reset ? 0.f : cmd1;
-    float t0 = cmd0, t1 = cmd1;
-    if (bias != 0.f) { t0 = t0 + bias; t1 = t1 + bias; }
-    if (c.act_noise_on) {
-      t0 = t0 + (u[SU_ACT] * K.act_rng + c.act_noise_min);
-      t1 = t1 + (u[SU_ACT + 1] * K.act_rng + c.act_noise_min);
-    }
-    t0 = clampt(t0, -1.f, 1.f);
-    t1 = clampt(t1, -1.f, 1.f);
-    float unit0 = c.affine_thrust ? 0.5f * (t0 + 1.0f) : clampt(t0, 0.f, 1.f);
-    float unit1 = c.affine_thrust ? 0.5f * (t1 + 1.0f) : clampt(t1, 0.f, 1.f);
-    unit0 = clampt(unit0, 0.f, 1.f);
-    unit1 = clampt(unit1, 0.f, 1.f);
-    const float uu0 = was_reset ? 0.f : unit0, uu1 = was_reset ? 0.f : unit1;
-    // ---- DynamicsFirstOrder.get_cmd_interpolated (ThrusterDynamics.py:179-219) ----
-    int i0 = (int)rintf(((uu0 + 1.0f) / 2.0f) * (float)(USV_LUT_N - 1));
-    int i1 = (int)rintf(((uu1 + 1.0f) / 2.0f) * (float)(USV_LUT_N - 1));
-    i0 = min(max(i0, 0), USV_LUT_N - 1);
-    i1 = min(max(i1, 0), USV_LUT_N - 1);
+    const ActionMap am = action_map(c, K, a2, was_reset, bias, u);
     bool mine = e < n;
     if (part == 1 || part == 2) mine = mine && ((part == 1) ? !was_reset : was_reset);
     // part 3: every env, but the envs reset this step leave their potential-dependent reward to
@@ -902,75 +1101,13 @@ __global__ __launch_bounds__(kBlock) void k_env_step(StepCfg ck, usv_bufs_t b, W
     reinterpret_cast<float4 *>(slut)[tid] = lut_a;
     if (lut_hi) reinterpret_cast<float4 *>(slut)[tid + kBlock] = lut_b;
     __syncthreads();   // LUT staged
-    float tgt0 = slut[i0], tgt1 = slut[USV_LUT_N + i1];
-    if (c.use_thr_mult) { tgt0 = tgt0 * thr_l; tgt1 = tgt1 * thr_r; }
-    // ---- 10 substeps: thruster lag, planar forces, semi-implicit Euler.  The
-    // integrator is this build's own (it replaces PhysX): accelerations divide by
-    // m and Izz through their reciprocals with one correction step (div_rn == the
-    // IEEE quotient for quotients in [2^-90, 2^120]) ----
-    const float izz = c.izz0 * k_iz;
-    const float inv_m = 1.0f / m, inv_izz = 1.0f / izz;
-    const float kd = c.use_drag_scale ? k_drag : 1.0f;
-    const float al = c.thr_alpha, oma = 1.0f - c.thr_alpha;
-    const float dt = c.dt;
-    const float arm_l = -(c.thr_y - comy), arm_r = c.thr_y + comy;
-    for (int s = 0; s < c.substeps; ++s) {
-      fl = fl * al + oma * tgt0;                      // ThrusterDynamics.py:133-136
-      fr = fr * al + oma * tgt1;
-      // the attitude the reference reads back: R = quaternion_to_matrix(q(yaw)) (usv_quat_rot)
-      const QuatRot qr = usv_quat_rot(yaw);
-      const float sy_ = qr.S, cy_ = qr.C;
-      float ub = cy_ * vx + sy_ * vy;                 // R^T v (Utils.py:10-14, Hydrodynamics.py:209-217)
-      float vb = -sy_ * vx + cy_ * vy;
-      float rb = wz;
-      float hpx = px, hpy = py;
-      if (kDist && c.current_on) {                    // relative to the water (Hydrodynamics.py:224-237)
-        ub = ub - (cy_ * c.flow_vel[0] + sy_ * c.flow_vel[1]);
-        vb = vb - (-sy_ * c.flow_vel[0] + cy_ * c.flow_vel[1]);
-      }
-      if (s == 0) {                                   // the cached pre-reset root state
-        ub = stl ? st_ub : ub;
-        vb = stl ? st_vb : vb;
-        rb = stl ? st_rb : rb;
-        hpx = stl ? st_px : hpx;
-        hpy = stl ? st_py : hpy;
-      }
-      float dfx = 0.f, dfy = 0.f, dtz = 0.f;
-      if (kDist) {
-        // get_disturbance_forces / get_torque_disturbance at root_pos (USV_disturbances.py:386-410,510-530)
-        const float wx = hpx + orgx, wy = hpy + orgy;
-        dfx = dp[DI_FCX];
-        dfy = dp[DI_FCY];
-        dtz = dp[DI_TC];
-        if (c.fsin_on) {
-          dfx = dfx + usv_sin_cr(wx * dp[DI_FXF] + dp[DI_FXS]) * dp[DI_FAMP];
-          dfy = dfy + usv_sin_cr(wy * dp[DI_FYF] + dp[DI_FYS]) * dp[DI_FAMP];
-        }
-        if (c.tsin_on) dtz = dtz + usv_sin_cr((wx + wy) * dp[DI_TF] + dp[DI_TS]) * dp[DI_TAMP];
-      }
-      float D0 = lin0 + qd0 * fabsf(ub), D1 = lin1 + qd1 * fabsf(vb), D2 = lin2 + qd2 * fabsf(rb);
-      D0 = D0 * c.scaling_damping; D1 = D1 * c.scaling_damping; D2 = D2 * c.scaling_damping;
-      if (c.use_drag_scale) { D0 = D0 * kd; D1 = D1 * kd; D2 = D2 * kd; }
-      // base force = disturbance + drag (+ hydrostatics, 0 in the plane), thrusters (USV_Virtual.py:1118-1132)
-      const float X = kDist ? fl + fr + (dfx + (-D0 * ub)) : fl + fr + (-D0 * ub);   // Hydrodynamics.py:243
-      const float Y = kDist ? dfy + (-D1 * vb) : -D1 * vb;
-      const float N = kDist ? arm_l * fl + arm_r * fr + (dtz + (-D2 * rb)) : arm_l * fl + arm_r * fr + (-D2 * rb);
-      const float ax = div_rn(cy_ * X - sy_ * Y, m, inv_m);
-      const float ay = div_rn(sy_ * X + cy_ * Y, m, inv_m);
-      const float aw = div_rn(N, izz, inv_izz);
-      vx = vx + ax * dt;
-      vy = vy + ay * dt;
-      wz = wz + aw * dt;
-      px = px + vx * dt;
-      py = py + vy * dt;
-      float yw = yaw + wz * dt;
-      if (yw > USV_PI_F) yw -= USV_2PI_F;
-      else if (yw <= -USV_PI_F) yw += USV_2PI_F;
-      yaw = yw;
-    }
-    bst(R, w.px, vs, px); bst(R, w.py, vs, py); bst(R, w.yaw, vs, yaw);
-    bst(R, w.vx, vs, vx); bst(R, w.vy, vs, vy); bst(R, w.wz, vs, wz);
-    bst(R, w.fl, vs, fl); bst(R, w.fr, vs, fr);
+    in.lut0 = slut[am.i0];
+    in.lut1 = slut[USV_LUT_N + am.i1];
+    in.m = m; in.k_iz = k_iz; in.k_drag = k_drag; in.thr_l = thr_l; in.thr_r = thr_r; in.comy = comy;
+    integrate_substeps(c, in, kDist, s);
+    bst(R, w.px, vs, s.px); bst(R, w.py, vs, s.py); bst(R, w.yaw, vs, s.yaw);
+    bst(R, w.vx, vs, s.vx); bst(R, w.vy, vs, s.vy); bst(R, w.wz, vs, s.wz);
+    bst(R, w.fl, vs, s.fl); bst(R, w.fr, vs, s.fr);
     // the rest of the step reads its config afresh (see StepCfg)
     const StepCfg ck2 = step_cfg_reload();
     const usv_cfg_t &c = ck2.c;
@@ -978,25 +1115,13 @@ __global__ __launch_bounds__(kBlock) void k_env_step(StepCfg ck, usv_bufs_t b, W
     // ---- post_physics_step: progress, update_state noise (USV_Virtual.py:771-813) ----
     const int progress = progress0 + 1;
     bsti(R, w.progress, vs, progress);
-    float pxn = px, pyn = py;
-    if (c.pos_noise_on) {
-      pxn = pxn + (u[SU_PX] * K.pos_rng + c.pos_noise_min);
-      pyn = pyn + (u[SU_PX + 1] * K.pos_rng + c.pos_noise_min);
-    }
+    const float2 pn = observed_position(c, K, u, s.px, s.py);
+    const float pxn = pn.x, pyn = pn.y;
     // the potential sample only needs the position: issue its 4 texel loads now
     const FieldTaps taps = field_taps(b.field + (size_t)ec * USV_FIELD_STRIDE, b.fnorm + (size_t)ec * USV_FNORM,
                                       c.map_size, pxn, pyn);
-    float vxn = vx, vyn = vy, wzn = wz;
-    if (c.vel_noise_on) {
-      vxn = vxn + (u[SU_VX] * K.vel_rng + c.vel_noise_min);
-      vyn = vyn + (u[SU_VY] * K.vel_rng + c.vel_noise_min);
-      wzn = wzn + (u[SU_WZ] * K.vel_rng + c.vel_noise_min);
-    }
-    // update_state's heading: atan2 of the read-back quaternion (USV_Virtual.py:776-786), then its noise
-    float yawn = usv_heading(usv_quat_rot(yaw));
-    if (c.head_noise_on) yawn = yawn + (u[SU_HEAD] * K.head_rng + c.head_noise_min);
-    float hs, hc;
-    usv_sincos(yawn, &hs, &hc);
+    const ObservedMotion om = observed_motion(c, K, u, s);
+    const float vxn = om.vxn, vyn = om.vyn, wzn = om.wzn, hs = om.hs, hc = om.hc;
     // ---- get_state_observations (static_obs.py:193-299) ----
     const float ex = tgx - pxn, ey = tgy - pyn;
     const float theta = usv_atan2(hs, hc);
@@ -1022,14 +1147,7 @@ __global__ __launch_bounds__(kBlock) void k_env_step(StepCfg ck, usv_bufs_t b, W
       sob[o][tid] = make_float2(obx[o], oby[o]);
     }
     top5_of_16(key);
-    if (c.obs_local) {
-      put(0, hc * vxn + hs * vyn);
-      put(1, -hs * vxn + hc * vyn);
-    } else {
-      put(0, vxn);
-      put(1, vyn);
-    }
-    put(2, wzn);
+    put_velocity_columns(c, om, put);
     put(3, ca);
     put(4, sa);
     put(5, dist_n);
@@ -1048,10 +1166,10 @@ __global__ __launch_bounds__(kBlock) void k_env_step(StepCfg ck, usv_bufs_t b, W
       put(10 + 3 * q, div_rn(-vby, nf, inv_nf));
     }
     const int pa = USV_NOBS_BASE - 2;
-    put(pa, prev_cmd0);
-    put(pa + 1, prev_cmd1);
-    bst(R, w.prev_cmd, vs, prev_cmd0);
-    bst(R, w.prev_cmd + w.n4, vs, prev_cmd1);
+    put(pa, am.prev_cmd0);
+    put(pa + 1, am.prev_cmd1);
+    bst(R, w.prev_cmd, vs, am.prev_cmd0);
+    bst(R, w.prev_cmd + w.n4, vs, am.prev_cmd1);
     // ---- privileged tail (USV_Virtual.py:840-976) ----
     write_priv_tail(c, K, m, comx, comy, comz, k_drag, thr_l, thr_r, k_iz, put);
     {   // the reward / kill / statistics section reads its config afresh too (see StepCfg)
@@ -1099,19 +1217,9 @@ __global__ __launch_bounds__(kBlock) void k_env_step(StepCfg ck, usv_bufs_t b, W
     rp.goal_r = ((float)goal_cnt * c.goal_reward) * 5.0f;
     rp.coll = coll;
     bst(R, w.prev_dist, vs, dist);
-    // ---- Penalties.compute_penalty (USV_task_rewards.py:440-523) ----
-    const float pact0 = c.pen_use_u ? unit0 : cmd0, pact1 = c.pen_use_u ? unit1 : cmd1;
-    float p_lin = 0.f, p_ang = 0.f, p_angv = 0.f, p_en = 0.f;
-    if (c.pen_lin_kind == PEN_NORM) p_lin = -tnorm2(vxn, vyn) * c.pen_lin_k + c.pen_lin_c;
-    if (c.pen_ang_kind) p_ang = pen_scalar(c.pen_ang_kind, c.pen_ang_k, c.pen_ang_x0, c.pen_ang_c, wzn);
-    if (c.pen_angv_kind) {
-      const float prev_w = pen_valid ? prev_wz_mem : wzn;
-      p_angv = pen_scalar(c.pen_angv_kind, c.pen_angv_k, c.pen_angv_x0, c.pen_angv_c, wzn - prev_w);
-    }
-    if (c.pen_en_kind == PEN_SUM) p_en = -(pact0 + pact1) * c.pen_en_k + c.pen_en_c;
-    else if (c.pen_en_kind == PEN_SUMSQ) p_en = -(pact0 * pact0 + pact1 * pact1) * c.pen_en_k + c.pen_en_c;
+    const StepPenalties pen = step_penalties(c, am, om, pen_valid, prev_wz_mem);
     bst(R, w.prev_wz, vs, wzn);
-    rp.pen_sum = ((p_lin + p_ang) + p_angv) + p_en;
+    rp.pen_sum = pen.sum;
     // ---- the potential-dependent tail ----
     const RewardOut ro = reward_tail(c, rp, field_blend(c, taps, [&](int o) { return sob[o][tid]; }, GridK{K.gstart, K.gend, K.gstep, b.grid_lin},
                                                  K.cell, K.inv_r, K.inv_safe), pot_none || was_reset, prev_pot_mem);
@@ -1140,18 +1248,18 @@ __global__ __launch_bounds__(kBlock) void k_env_step(StepCfg ck, usv_bufs_t b, W
     __builtin_amdgcn_raw_buffer_store_b64(rb64, R, mine ? (uint32_t)ec * 8u : kDrop, w.dones, 0);
     __builtin_amdgcn_raw_buffer_store_b8((uint8_t)0, R, mine ? (uint32_t)ec : kDrop, w.just_reset, 0);
     if (c.nan_probe) {   // clamped actions, the observed state, the reward (obs: at the row store below)
-      uint32_t bits = ((nonfinite(cmd0) | nonfinite(cmd1)) ? USV_NAN_ACTIONS : 0u) |
-                      ((nonfinite(pxn) | nonfinite(pyn) | nonfinite(yawn) | nonfinite(vxn) | nonfinite(vyn) |
-                        nonfinite(wzn)) ? USV_NAN_STATE : 0u) |
-                      ((!defer && nonfinite(ro.rew)) ? USV_NAN_REWARD : 0u);
+      const uint32_t bits = nan_bits_actions_state(am, pn, om) | ((!defer && nonfinite(ro.rew)) ? USV_NAN_REWARD : 0u);
       nan_report(&b.ctl[USV_CTL_NAN_FLAG], mine ? bits : 0u);
     }
     if (kStats) {
+      const StateStats ss = state_stats(am, om);
+      static_assert(kSum[19] == kStateStatKey[0] && kSum[20] == kStateStatKey[1] && kSum[21] == kStateStatKey[2] &&
+                    kSum[22] == kStateStatKey[3] && kSum[23] == kStateStatKey[4] && kSum[24] == kStateStatKey[5],
+                    "kSum ends in the state statistics");
       const float add[25] = {ro.total, ro.dist_r, ro.align_r, rp.hi_r, ro.shaping, rp.speed_r, rp.ang_r, ro.turn_haz,
                              rp.goal_r, c.time_reward, coll, ro.danger, (float)(ro.danger > 0.5f), ro.gate_pos, dist,
-                             bpen, p_ang, p_angv, p_en, tnorm2(vxn, vyn), fabsf(wzn),
-                             ((float)(t0 < 0.f) + (float)(t1 < 0.f)) / 2.0f, (unit0 + unit1) / 2.0f,
-                             ((float)(unit0 < 0.05f) + (float)(unit1 < 0.05f)) / 2.0f, unit0 + unit1};
+                             bpen, pen.p_ang, pen.p_angv, pen.p_en,
+                             ss.v[0], ss.v[1], ss.v[2], ss.v[3], ss.v[4], ss.v[5]};
 #pragma unroll
       for (int q = 0; q < 25; ++q)
         if (sum_on[q]) bst(R, w.stats + (uint32_t)kSum[q] * w.n4, stat_of_reward(kSum[q]) ? vr : vs, sums[q] + add[q]);
@@ -1245,8 +1353,10 @@ __global__ __launch_bounds__(64) void k_env_reward_late(usv_cfg_t c, usv_bufs_t 
 }
 
 // ------------------------------------------------------------------------
-// GoToPose / TrackXYOVelocity control step.  Same physics, action
-// mapping, noise, penalties and privileged tail as the CaptureXY step; the task
+// GoToPose / TrackXYOVelocity control step.  The action map, the substeps, the observed state, the
+// penalties, the NaN probe's action / state bits, the state statistics and the privileged tail are the functions
+// the CaptureXY step calls (action_map, integrate_substeps, observed_position / observed_motion,
+// put_velocity_columns, step_penalties, nan_bits_actions_state, state_stats, write_priv_tail); the task
 // part follows GoToPoseTask (tasks/USV/USV_go_to_pose.py:89-209) and
 // TrackXYOVelocityTask (USV_track_xyo_velocity.py:75-166) with their rewards
 // (USV_task_rewards.py:160-249, 328-393).  Glue where the reference cannot run
@@ -1295,23 +1405,22 @@ __global__ __launch_bounds__(kBlock) void k_env_step_task(StepCfg ck, usv_bufs_t
   // ---- loads ----
   const float2 a2 = reinterpret_cast<const float2 *>(actions)[ec];
   const bool was_reset = b.just_reset[ec] != 0;
-  float px = b.px[ec], py = b.py[ec], yaw = b.yaw[ec], vx = b.vx[ec], vy = b.vy[ec], wz = b.wz[ec];
-  float fl = b.fl[ec], fr = b.fr[ec];
+  BodyState s{b.px[ec], b.py[ec], b.yaw[ec], b.vx[ec], b.vy[ec], b.wz[ec], b.fl[ec], b.fr[ec]};
   const float m = b.mass[ec], k_iz = b.k_iz[ec], k_drag = b.k_drag[ec];
   const float thr_l = b.thr_l[ec], thr_r = b.thr_r[ec];
   const float comx = b.com_x[ec], comy = b.com_y[ec], comz = b.com_z[ec];
-  float lin0 = c.lin_damp[0], lin1 = c.lin_damp[1], lin2 = c.lin_damp[2];
-  float qd0 = c.quad_damp[0], qd1 = c.quad_damp[1], qd2 = c.quad_damp[2];
-  if (b.lin_damp) {
-    lin0 = b.lin_damp[ec]; lin1 = b.lin_damp[nn + ec]; lin2 = b.lin_damp[2 * nn + ec];
-    qd0 = b.quad_damp[ec]; qd1 = b.quad_damp[nn + ec]; qd2 = b.quad_damp[2 * nn + ec];
-  }
-  float dp[USV_NDIST], orgx = 0.f, orgy = 0.f;
+  SubstepIn in;
+  in.damp = Damping{c.lin_damp[0], c.lin_damp[1], c.lin_damp[2], c.quad_damp[0], c.quad_damp[1], c.quad_damp[2]};
+  if (b.lin_damp)
+    in.damp = Damping{b.lin_damp[ec], b.lin_damp[nn + ec], b.lin_damp[2 * nn + ec],
+                      b.quad_damp[ec], b.quad_damp[nn + ec], b.quad_damp[2 * nn + ec]};
+  in.orgx = 0.f;
+  in.orgy = 0.f;
   const bool has_dist = b.dist != nullptr;
   if (has_dist) {
 #pragma unroll
-    for (int q = 0; q < USV_NDIST; ++q) dp[q] = b.dist[q * nn + ec];
-    if (b.env_org) { orgx = b.env_org[ec]; orgy = b.env_org[nn + ec]; }
+    for (int q = 0; q < USV_NDIST; ++q) in.dp[q] = b.dist[q * nn + ec];
+    if (b.env_org) { in.orgx = b.env_org[ec]; in.orgy = b.env_org[nn + ec]; }
   }
   const int progress0 = b.progress[ec], goal_cnt0 = b.goal_cnt[ec];
   constexpr bool kHasH = kKind == USV_TASK_GO_TO_POSE || kKind == USV_TASK_TRACK_XYO;   // the kinds with a tgt_h
@@ -1321,14 +1430,14 @@ __global__ __launch_bounds__(kBlock) void k_env_step_task(StepCfg ck, usv_bufs_t
   const float prev_asum = c.pen_actv_kind ? b.prev_head[ec] : 0.f;
   const bool rew_valid = b.ctl[USV_CTL_REW_VALID] != 0;
   // a reset env's first substep: the pre-reset inputs usv_reset kept
-  const bool stl = c.stale_root && was_reset;
-  float st_ub = 0.f, st_vb = 0.f, st_rb = 0.f, st_px = 0.f, st_py = 0.f;
-  if (stl) {
-    st_ub = b.stale[USV_STALE_UB * nn + ec];
-    st_vb = b.stale[USV_STALE_VB * nn + ec];
-    st_rb = b.stale[USV_STALE_RB * nn + ec];
-    st_px = b.stale[USV_STALE_PX * nn + ec];
-    st_py = b.stale[USV_STALE_PY * nn + ec];
+  in.stl = c.stale_root && was_reset;
+  in.st_ub = in.st_vb = in.st_rb = in.st_px = in.st_py = 0.f;
+  if (in.stl) {
+    in.st_ub = b.stale[USV_STALE_UB * nn + ec];
+    in.st_vb = b.stale[USV_STALE_VB * nn + ec];
+    in.st_rb = b.stale[USV_STALE_RB * nn + ec];
+    in.st_px = b.stale[USV_STALE_PX * nn + ec];
+    in.st_py = b.stale[USV_STALE_PY * nn + ec];
   }
   float sums[USV_NSTAT];
   if (kStats) {
@@ -1344,84 +1453,16 @@ __global__ __launch_bounds__(kBlock) void k_env_step_task(StepCfg ck, usv_bufs_t
     if (c.pos_noise_on || c.act_noise_on) philox_u4(seed, (uint32_t)e, step, 1u, u + 4);
     else u[4] = u[5] = u[6] = u[7] = 0.f;
   }
-  // ---- VecEnvRLGames.step clamp + pre_physics_step (USV_Virtual.py:1050-1099) ----
-  const float cmd0 = clampt(a2.x, -c.clip_actions, c.clip_actions);
-  const float cmd1 = clampt(a2.y, -c.clip_actions, c.clip_actions);
-  const float prev_cmd0 = was_reset ? 0.f : cmd0, prev_cmd1 = was_reset ? 0.f : cmd1;
-  float t0 = cmd0, t1 = cmd1;
-  if (bias != 0.f) { t0 = t0 + bias; t1 = t1 + bias; }
-  if (c.act_noise_on) {
-    t0 = t0 + (u[SU_ACT] * K.act_rng + c.act_noise_min);
-    t1 = t1 + (u[SU_ACT + 1] * K.act_rng + c.act_noise_min);
-  }
-  t0 = clampt(t0, -1.f, 1.f);
-  t1 = clampt(t1, -1.f, 1.f);
-  float unit0 = c.affine_thrust ? 0.5f * (t0 + 1.0f) : clampt(t0, 0.f, 1.f);
-  float unit1 = c.affine_thrust ? 0.5f * (t1 + 1.0f) : clampt(t1, 0.f, 1.f);
-  unit0 = clampt(unit0, 0.f, 1.f);
-  unit1 = clampt(unit1, 0.f, 1.f);
-  const float uu0 = was_reset ? 0.f : unit0, uu1 = was_reset ? 0.f : unit1;
-  int i0 = (int)rintf(((uu0 + 1.0f) / 2.0f) * (float)(USV_LUT_N - 1));
-  int i1 = (int)rintf(((uu1 + 1.0f) / 2.0f) * (float)(USV_LUT_N - 1));
-  i0 = min(max(i0, 0), USV_LUT_N - 1);
-  i1 = min(max(i1, 0), USV_LUT_N - 1);
-  float tgt0 = lut[i0], tgt1 = lut[USV_LUT_N + i1];
-  if (c.use_thr_mult) { tgt0 = tgt0 * thr_l; tgt1 = tgt1 * thr_r; }
-  // ---- substeps: the CaptureXY step's integrator (thruster lag, planar forces, semi-implicit Euler) ----
-  const float izz = c.izz0 * k_iz;
-  const float inv_m = 1.0f / m, inv_izz = 1.0f / izz;
-  const float kd = c.use_drag_scale ? k_drag : 1.0f;
-  const float al = c.thr_alpha, oma = 1.0f - c.thr_alpha;
-  const float dt = c.dt;
-  const float arm_l = -(c.thr_y - comy), arm_r = c.thr_y + comy;
-  for (int s = 0; s < c.substeps; ++s) {
-    fl = fl * al + oma * tgt0;
-    fr = fr * al + oma * tgt1;
-    const QuatRot qr = usv_quat_rot(yaw);   // R = quaternion_to_matrix(q(yaw)), as the CaptureXY step
-    const float sy_ = qr.S, cy_ = qr.C;
-    float ub = cy_ * vx + sy_ * vy;
-    float vb = -sy_ * vx + cy_ * vy;
-    float rb = wz;
-    float hpx = px, hpy = py;
-    if (has_dist && c.current_on) {
-      ub = ub - (cy_ * c.flow_vel[0] + sy_ * c.flow_vel[1]);
-      vb = vb - (-sy_ * c.flow_vel[0] + cy_ * c.flow_vel[1]);
-    }
-    if (s == 0 && stl) { ub = st_ub; vb = st_vb; rb = st_rb; hpx = st_px; hpy = st_py; }
-    float dfx = 0.f, dfy = 0.f, dtz = 0.f;
-    if (has_dist) {
-      const float wx = hpx + orgx, wy = hpy + orgy;
-      dfx = dp[DI_FCX];
-      dfy = dp[DI_FCY];
-      dtz = dp[DI_TC];
-      if (c.fsin_on) {
-        dfx = dfx + usv_sin_cr(wx * dp[DI_FXF] + dp[DI_FXS]) * dp[DI_FAMP];
-        dfy = dfy + usv_sin_cr(wy * dp[DI_FYF] + dp[DI_FYS]) * dp[DI_FAMP];
-      }
-      if (c.tsin_on) dtz = dtz + usv_sin_cr((wx + wy) * dp[DI_TF] + dp[DI_TS]) * dp[DI_TAMP];
-    }
-    float D0 = lin0 + qd0 * fabsf(ub), D1 = lin1 + qd1 * fabsf(vb), D2 = lin2 + qd2 * fabsf(rb);
-    D0 = D0 * c.scaling_damping; D1 = D1 * c.scaling_damping; D2 = D2 * c.scaling_damping;
-    if (c.use_drag_scale) { D0 = D0 * kd; D1 = D1 * kd; D2 = D2 * kd; }
-    const float X = has_dist ? fl + fr + (dfx + (-D0 * ub)) : fl + fr + (-D0 * ub);
-    const float Y = has_dist ? dfy + (-D1 * vb) : -D1 * vb;
-    const float N = has_dist ? arm_l * fl + arm_r * fr + (dtz + (-D2 * rb)) : arm_l * fl + arm_r * fr + (-D2 * rb);
-    const float ax = div_rn(cy_ * X - sy_ * Y, m, inv_m);
-    const float ay = div_rn(sy_ * X + cy_ * Y, m, inv_m);
-    const float aw = div_rn(N, izz, inv_izz);
-    vx = vx + ax * dt;
-    vy = vy + ay * dt;
-    wz = wz + aw * dt;
-    px = px + vx * dt;
-    py = py + vy * dt;
-    float yw = yaw + wz * dt;
-    if (yw > USV_PI_F) yw -= USV_2PI_F;
-    else if (yw <= -USV_PI_F) yw += USV_2PI_F;
-    yaw = yw;
-  }
+  // ---- the shared step: action map, substeps (the LUT read is this kernel's: global memory) ----
+  const ActionMap am = action_map(c, K, a2, was_reset, bias, u);
+  const float cmd0 = am.cmd0, cmd1 = am.cmd1;
+  in.lut0 = lut[am.i0];
+  in.lut1 = lut[USV_LUT_N + am.i1];
+  in.m = m; in.k_iz = k_iz; in.k_drag = k_drag; in.thr_l = thr_l; in.thr_r = thr_r; in.comy = comy;
+  integrate_substeps(c, in, has_dist, s);
   if (mine) {
-    b.px[e] = px; b.py[e] = py; b.yaw[e] = yaw; b.vx[e] = vx; b.vy[e] = vy; b.wz[e] = wz;
-    b.fl[e] = fl; b.fr[e] = fr;
+    b.px[e] = s.px; b.py[e] = s.py; b.yaw[e] = s.yaw; b.vx[e] = s.vx; b.vy[e] = s.vy; b.wz[e] = s.wz;
+    b.fl[e] = s.fl; b.fr[e] = s.fr;
   }
   {   // the rest of the step reads its config afresh (see StepCfg)
   const StepCfg ck2 = step_cfg_reload();
@@ -1429,52 +1470,23 @@ __global__ __launch_bounds__(kBlock) void k_env_step_task(StepCfg ck, usv_bufs_t
   const StepK &K = ck2.K;
   // ---- post_physics_step: progress, update_state noise (USV_Virtual.py:771-813) ----
   const int progress = progress0 + 1;
-  float pxn = px, pyn = py;
-  if (c.pos_noise_on) {
-    pxn = pxn + (u[SU_PX] * K.pos_rng + c.pos_noise_min);
-    pyn = pyn + (u[SU_PX + 1] * K.pos_rng + c.pos_noise_min);
-  }
-  float vxn = vx, vyn = vy, wzn = wz;
-  if (c.vel_noise_on) {
-    vxn = vxn + (u[SU_VX] * K.vel_rng + c.vel_noise_min);
-    vyn = vyn + (u[SU_VY] * K.vel_rng + c.vel_noise_min);
-    wzn = wzn + (u[SU_WZ] * K.vel_rng + c.vel_noise_min);
-  }
-  float yawn = usv_heading(usv_quat_rot(yaw));   // update_state's heading (USV_Virtual.py:776-786)
-  if (c.head_noise_on) yawn = yawn + (u[SU_HEAD] * K.head_rng + c.head_noise_min);
-  float hs, hc;
-  usv_sincos(yawn, &hs, &hc);
+  const float2 pn = observed_position(c, K, u, s.px, s.py);
+  const ObservedMotion om = observed_motion(c, K, u, s);
+  const float pxn = pn.x, pyn = pn.y, vxn = om.vxn, vyn = om.vyn, wzn = om.wzn, hs = om.hs, hc = om.hc;
   // ---- Core.update_observation_tensor (USV_core.py:55-121) ----
-  if (c.obs_local) {
-    put(0, hc * vxn + hs * vyn);
-    put(1, -hs * vxn + hc * vyn);
-  } else {
-    put(0, vxn);
-    put(1, vyn);
-  }
-  put(2, wzn);
+  put_velocity_columns(c, om, put);
 #pragma unroll
   for (int q = 3; q < USV_NOBS - 10; ++q) obs[q] = 0.f;   // task_data columns no task writes
   const int pa = USV_NOBS_BASE - 2;
   if (c.priv_dim == 4) { obs[29] = 0.f; obs[30] = 0.f; obs[31] = 0.f; obs[32] = 0.f; }   // input padding
-  put(pa, prev_cmd0);
-  put(pa + 1, prev_cmd1);
+  put(pa, am.prev_cmd0);
+  put(pa + 1, am.prev_cmd1);
   write_priv_tail(c, K, m, comx, comy, comz, k_drag, thr_l, thr_r, k_iz, put);
   {
   const StepCfg ck3 = step_cfg_reload();
   const usv_cfg_t &c = ck3.c;
   const StepK &K = ck3.K;
-  // ---- Penalties.compute_penalty (USV_task_rewards.py:440-523) ----
-  const float pact0 = c.pen_use_u ? unit0 : cmd0, pact1 = c.pen_use_u ? unit1 : cmd1;
-  float p_lin = 0.f, p_ang = 0.f, p_angv = 0.f, p_en = 0.f;
-  if (c.pen_lin_kind == PEN_NORM) p_lin = -tnorm2(vxn, vyn) * c.pen_lin_k + c.pen_lin_c;
-  if (c.pen_ang_kind) p_ang = pen_scalar(c.pen_ang_kind, c.pen_ang_k, c.pen_ang_x0, c.pen_ang_c, wzn);
-  if (c.pen_angv_kind) {
-    const float prev_w = pen_valid ? prev_wz_mem : wzn;
-    p_angv = pen_scalar(c.pen_angv_kind, c.pen_angv_k, c.pen_angv_x0, c.pen_angv_c, wzn - prev_w);
-  }
-  if (c.pen_en_kind == PEN_SUM) p_en = -(pact0 + pact1) * c.pen_en_k + c.pen_en_c;
-  else if (c.pen_en_kind == PEN_SUMSQ) p_en = -(pact0 * pact0 + pact1 * pact1) * c.pen_en_k + c.pen_en_c;
+  const StepPenalties pen = step_penalties(c, am, om, pen_valid, prev_wz_mem);
   // penalize_action_variation (:497-506): sum(actions) - sum(prev_actions).  With penalties_use_thrust_u the
   // reference hands compute_penalty its persistent thrust_cmds_unit tensor (USV_Virtual.py:1095, 1634-1639) and
   // keeps that same object as prev_actions (:515), so the difference is identically 0; without it the actions
@@ -1485,8 +1497,7 @@ __global__ __launch_bounds__(kBlock) void k_env_step_task(StepCfg ck, usv_bufs_t
     const float dsum = (c.pen_use_u || !pen_valid) ? 0.f : asum - prev_asum;
     p_actv = pen_scalar(c.pen_actv_kind, c.pen_actv_k, c.pen_actv_x0, c.pen_actv_c, dsum);
   }
-  const float pen_base = ((p_lin + p_ang) + p_angv) + p_en;
-  const float pen_sum = c.pen_actv_kind ? pen_base + p_actv : pen_base;
+  const float pen_sum = c.pen_actv_kind ? pen.sum + p_actv : pen.sum;
   const int tout = progress >= c.max_episode_length - 1;
   float t_add[5];
   t_add[4] = 0.f;
@@ -1607,8 +1618,8 @@ __global__ __launch_bounds__(kBlock) void k_env_step_task(StepCfg ck, usv_bufs_t
   }
   if (mine) {
     b.progress[e] = progress;
-    b.prev_cmd[e] = prev_cmd0;
-    b.prev_cmd[nn + e] = prev_cmd1;
+    b.prev_cmd[e] = am.prev_cmd0;
+    b.prev_cmd[nn + e] = am.prev_cmd1;
     b.prev_wz[e] = wzn;
     if (c.pen_actv_kind) b.prev_head[e] = asum;
     b.just_reset[e] = 0;
@@ -1621,21 +1632,17 @@ __global__ __launch_bounds__(kBlock) void k_env_step_task(StepCfg ck, usv_bufs_t
       b.dones[e] = rb;
     }
     if (kStats) {
-      const float vn = tnorm2(vxn, vyn);
+      const StateStats ss = state_stats(am, om);
       float add[USV_NSTAT];
 #pragma unroll
       for (int q = 0; q < USV_NSTAT; ++q) add[q] = 0.f;
       add[0] = t_add[0]; add[1] = t_add[1]; add[2] = t_add[2]; add[3] = t_add[3]; add[4] = t_add[4];
       add[USV_ST_ACTION_VARIATION] = p_actv;
-      add[ST_ANGULAR_VEL_PENALTY] = p_ang;
-      add[ST_ANGULAR_VEL_VARIATION_PENALTY] = p_angv;
-      add[ST_ENERGY_PENALTY] = p_en;
-      add[ST_NORMED_LINEAR_VEL] = vn;
-      add[ST_NORMED_ANGULAR_VEL] = fabsf(wzn);
-      add[ST_CMD_NEG_RATE] = ((float)(t0 < 0.f) + (float)(t1 < 0.f)) / 2.0f;
-      add[ST_U_MEAN] = (unit0 + unit1) / 2.0f;
-      add[ST_U_LOW_RATE] = ((float)(unit0 < 0.05f) + (float)(unit1 < 0.05f)) / 2.0f;
-      add[ST_U_SUM] = unit0 + unit1;
+      add[ST_ANGULAR_VEL_PENALTY] = pen.p_ang;
+      add[ST_ANGULAR_VEL_VARIATION_PENALTY] = pen.p_angv;
+      add[ST_ENERGY_PENALTY] = pen.p_en;
+#pragma unroll
+      for (int q = 0; q < 6; ++q) add[kStateStatKey[q]] = ss.v[q];
 #pragma unroll
       for (int q = 0; q < USV_NSTAT; ++q)
         if (q != ST_SUCCESS && q != ST_COLLISION && (kKind != USV_TASK_TRACK_XYO || (q != 2 && q != 3)))
@@ -1659,10 +1666,8 @@ __global__ __launch_bounds__(kBlock) void k_env_step_task(StepCfg ck, usv_bufs_t
     ob[i] = sobs[i];
   }
   if (c.nan_probe) {   // clamped actions, the observed state, the reward (TrackXYO: k_track_finish), obs
-    uint32_t bits = ((nonfinite(cmd0) | nonfinite(cmd1)) ? USV_NAN_ACTIONS : 0u) |
-                    ((nonfinite(pxn) | nonfinite(pyn) | nonfinite(yawn) | nonfinite(vxn) | nonfinite(vyn) |
-                      nonfinite(wzn)) ? USV_NAN_STATE : 0u) |
-                    ((kKind != USV_TASK_TRACK_XYO && nonfinite(overall + pen_sum)) ? USV_NAN_REWARD : 0u);
+    const uint32_t bits = nan_bits_actions_state(am, pn, om) |
+                          ((kKind != USV_TASK_TRACK_XYO && nonfinite(overall + pen_sum)) ? USV_NAN_REWARD : 0u);
     nan_report(&b.ctl[USV_CTL_NAN_FLAG], (mine ? bits : 0u) | (obad ? USV_NAN_OBS : 0u));
   }
   if (blockIdx.x == 0 && tid == 0) b.ctl[USV_CTL_STEPPED] = 1;
@@ -1766,53 +1771,68 @@ __global__ void k_forces(usv_cfg_t c, usv_bufs_t b, float *__restrict__ out) {
     ub = ub - (cy_ * c.flow_vel[0] + sy_ * c.flow_vel[1]);
     vb = vb - (-sy_ * c.flow_vel[0] + cy_ * c.flow_vel[1]);
   }
-  float lin0 = c.lin_damp[0], lin1 = c.lin_damp[1], lin2 = c.lin_damp[2];
-  float qd0 = c.quad_damp[0], qd1 = c.quad_damp[1], qd2 = c.quad_damp[2];
-  if (b.lin_damp) {
-    lin0 = b.lin_damp[e]; lin1 = b.lin_damp[n + e]; lin2 = b.lin_damp[2 * n + e];
-    qd0 = b.quad_damp[e]; qd1 = b.quad_damp[n + e]; qd2 = b.quad_damp[2 * n + e];
-  }
-  float D0 = (lin0 + qd0 * fabsf(ub)) * c.scaling_damping;
-  float D1 = (lin1 + qd1 * fabsf(vb)) * c.scaling_damping;
-  float D2 = (lin2 + qd2 * fabsf(wz)) * c.scaling_damping;
-  if (c.use_drag_scale) { const float k = b.k_drag[e]; D0 *= k; D1 *= k; D2 *= k; }
+  Damping d{c.lin_damp[0], c.lin_damp[1], c.lin_damp[2], c.quad_damp[0], c.quad_damp[1], c.quad_damp[2]};
+  if (b.lin_damp)
+    d = Damping{b.lin_damp[e], b.lin_damp[n + e], b.lin_damp[2 * n + e],
+                b.quad_damp[e], b.quad_damp[n + e], b.quad_damp[2 * n + e]};
+  // the damping expression the step kernels integrate
+  const Drag3 D = drag_coeffs(c, d, c.use_drag_scale ? b.k_drag[e] : 1.0f, ub, vb, wz);
   const float fl = b.fl[e], fr = b.fr[e], comy = b.com_y[e];
-  out[3 * e] = fl + fr + (-D0 * ub);
-  out[3 * e + 1] = -D1 * vb;
-  out[3 * e + 2] = -(c.thr_y - comy) * fl + (c.thr_y + comy) * fr + (-D2 * wz);
+  out[3 * e] = fl + fr + (-D.D0 * ub);
+  out[3 * e + 1] = -D.D1 * vb;
+  out[3 * e + 2] = -(c.thr_y - comy) * fl + (c.thr_y + comy) * fr + (-D.D2 * wz);
 }
 
 // ---- host side of the step launch ----
+// k_env_step's per-env arrays: where each lies, its size, the StepWin member that takes its window offset, its
+// row in the canonical slab (include/usv_hip.h USV_SLAB_*) and whether the step can run without it
+struct StepArr {
+  const void *p;
+  size_t bytes;
+  uint32_t StepWin::*off;
+  int row;
+  bool required = true;
+};
+constexpr int kStepArrs = 39;
+std::array<StepArr, kStepArrs> step_arrays(const usv_cfg_t &c, const usv_bufs_t &b) {
+  const size_t n = (size_t)b.n, f = n * 4;
+  // quad_damp is read with lin_damp only; stats / stale when the config turns them on
+  const bool dr = b.lin_damp != nullptr, st = c.stats_on != 0, sr = c.stale_root != 0;
+  return {{{b.px, f, &StepWin::px, USV_SLAB_STATE}, {b.py, f, &StepWin::py, USV_SLAB_STATE + 1},
+          {b.yaw, f, &StepWin::yaw, USV_SLAB_STATE + 2}, {b.vx, f, &StepWin::vx, USV_SLAB_STATE + 3},
+          {b.vy, f, &StepWin::vy, USV_SLAB_STATE + 4}, {b.wz, f, &StepWin::wz, USV_SLAB_STATE + 5},
+          {b.fl, f, &StepWin::fl, USV_SLAB_STATE + 6}, {b.fr, f, &StepWin::fr, USV_SLAB_STATE + 7},
+          {b.mass, f, &StepWin::mass, USV_SLAB_PARAMS}, {b.com_x, f, &StepWin::com_x, USV_SLAB_PARAMS + 1},
+          {b.com_y, f, &StepWin::com_y, USV_SLAB_PARAMS + 2}, {b.com_z, f, &StepWin::com_z, USV_SLAB_PARAMS + 3},
+          {b.k_drag, f, &StepWin::k_drag, USV_SLAB_PARAMS + 4}, {b.thr_l, f, &StepWin::thr_l, USV_SLAB_PARAMS + 5},
+          {b.thr_r, f, &StepWin::thr_r, USV_SLAB_PARAMS + 6}, {b.k_iz, f, &StepWin::k_iz, USV_SLAB_PARAMS + 7},
+          {b.lin_damp, 3 * f, &StepWin::lin_damp, USV_SLAB_LIN_DAMP, false},
+          {dr ? b.quad_damp : nullptr, 3 * f, &StepWin::quad_damp, USV_SLAB_QUAD_DAMP, dr},
+          {b.tgt_x, f, &StepWin::tgt_x, USV_SLAB_TGT}, {b.tgt_y, f, &StepWin::tgt_y, USV_SLAB_TGT + 1},
+          {b.obst, 2 * USV_NOBST * f, &StepWin::obst, USV_SLAB_OBST},
+          {b.prev_cmd, 2 * f, &StepWin::prev_cmd, USV_SLAB_PREV_CMD},
+          {b.prev_dist, f, &StepWin::prev_dist, USV_SLAB_HIST},
+          {b.prev_head, f, &StepWin::prev_head, USV_SLAB_HIST + 1},
+          {b.prev_pot, f, &StepWin::prev_pot, USV_SLAB_HIST + 2}, {b.prev_wz, f, &StepWin::prev_wz, USV_SLAB_HIST + 3},
+          {b.goal_cnt, f, &StepWin::goal_cnt, USV_SLAB_IBUF}, {b.progress, f, &StepWin::progress, USV_SLAB_IBUF + 1},
+          {b.reset_buf, f, &StepWin::reset_buf, USV_SLAB_IBUF + 2},
+          {b.done_succ, f, &StepWin::done_succ, USV_SLAB_IBUF + 3},
+          {b.done_coll, f, &StepWin::done_coll, USV_SLAB_IBUF + 4},
+          {b.just_reset, n, &StepWin::just_reset, USV_SLAB_JUST_RESET},
+          {st ? b.stats : nullptr, USV_NSTAT * f, &StepWin::stats, USV_SLAB_STATS, st},
+          {b.obs, USV_NOBS * f, &StepWin::obs, USV_SLAB_OBS}, {b.rew, f, &StepWin::rew, USV_SLAB_REW},
+          {b.dones, 2 * f, &StepWin::dones, USV_SLAB_DONES},
+          {b.dist, USV_NDIST * f, &StepWin::dist, USV_SLAB_DIST, false},
+          {b.dist ? b.env_org : nullptr, 2 * f, &StepWin::env_org, USV_SLAB_ENV_ORG, false},
+          {sr ? b.stale : nullptr, USV_STALE_ROWS * f, &StepWin::stale, USV_SLAB_STALE, sr}}};
+}
+
 // byte offsets of the step kernel's per-env arrays inside one window; status 2 when
 // they span 2 GiB or more (allocate them from one slab, as tasks/usv_virtual.py does)
 int step_window(const usv_cfg_t &c, const usv_bufs_t &b, const char **base, StepWin *w) {
-  const size_t n = (size_t)b.n, f = n * 4;
-  struct Arr {
-    const void *p;
-    size_t bytes;
-    uint32_t *off;
-    bool required;
-  };
-  const Arr arr[] = {
-      {b.px, f, &w->px, true}, {b.py, f, &w->py, true}, {b.yaw, f, &w->yaw, true}, {b.vx, f, &w->vx, true},
-      {b.vy, f, &w->vy, true}, {b.wz, f, &w->wz, true}, {b.fl, f, &w->fl, true}, {b.fr, f, &w->fr, true},
-      {b.mass, f, &w->mass, true}, {b.k_iz, f, &w->k_iz, true}, {b.k_drag, f, &w->k_drag, true},
-      {b.thr_l, f, &w->thr_l, true}, {b.thr_r, f, &w->thr_r, true}, {b.com_x, f, &w->com_x, true},
-      {b.com_y, f, &w->com_y, true}, {b.com_z, f, &w->com_z, true}, {b.lin_damp, 3 * f, &w->lin_damp, false},
-      {b.lin_damp ? b.quad_damp : nullptr, 3 * f, &w->quad_damp, b.lin_damp != nullptr},
-      {b.progress, f, &w->progress, true}, {b.tgt_x, f, &w->tgt_x, true}, {b.tgt_y, f, &w->tgt_y, true},
-      {b.obst, 2 * USV_NOBST * f, &w->obst, true}, {b.goal_cnt, f, &w->goal_cnt, true},
-      {b.prev_dist, f, &w->prev_dist, true}, {b.prev_head, f, &w->prev_head, true},
-      {b.prev_pot, f, &w->prev_pot, true}, {b.prev_wz, f, &w->prev_wz, true},
-      {c.stats_on ? b.stats : nullptr, USV_NSTAT * f, &w->stats, c.stats_on != 0},
-      {b.prev_cmd, 2 * f, &w->prev_cmd, true}, {b.rew, f, &w->rew, true}, {b.reset_buf, f, &w->reset_buf, true},
-      {b.dones, 2 * f, &w->dones, true}, {b.done_coll, f, &w->done_coll, true},
-      {b.done_succ, f, &w->done_succ, true}, {b.just_reset, n, &w->just_reset, true},
-      {b.obs, USV_NOBS * f, &w->obs, true}, {b.dist, USV_NDIST * f, &w->dist, false},
-      {b.dist ? b.env_org : nullptr, 2 * f, &w->env_org, false},
-      {c.stale_root ? b.stale : nullptr, USV_STALE_ROWS * f, &w->stale, c.stale_root != 0}};
+  const auto arr = step_arrays(c, b);
   uintptr_t lo = UINTPTR_MAX, hi = 0;
-  for (const Arr &a : arr) {
+  for (const StepArr &a : arr) {
     if (!a.p) {
       if (a.required) return 1;
       continue;
@@ -1821,8 +1841,8 @@ int step_window(const usv_cfg_t &c, const usv_bufs_t &b, const char **base, Step
     hi = std::max(hi, (uintptr_t)a.p + a.bytes);
   }
   if (hi - lo >= 0x7FFFFFFFull) return 2;
-  for (const Arr &a : arr) *a.off = a.p ? (uint32_t)((uintptr_t)a.p - lo) : 0u;
-  w->n4 = (uint32_t)f;
+  for (const StepArr &a : arr) w->*a.off = a.p ? (uint32_t)((uintptr_t)a.p - lo) : 0u;
+  w->n4 = (uint32_t)(4 * (size_t)b.n);
   w->bytes = (uint32_t)(hi - lo);
   *base = (const char *)lo;
   return 0;
@@ -1836,36 +1856,32 @@ int fixed_slab_shift(const usv_cfg_t &c, const usv_bufs_t &b) {
   if (sh < kFixedShiftMin || sh > kFixedShiftMax || !b.px) return -1;
   const char *base = reinterpret_cast<const char *>(b.px);
   const size_t rb = (size_t)1 << sh;
-  struct Row {
-    const void *p;
-    int row;
-    bool required;
-  };
-  const Row rows[] = {
-      {b.px, USV_SLAB_STATE, true}, {b.py, USV_SLAB_STATE + 1, true}, {b.yaw, USV_SLAB_STATE + 2, true},
-      {b.vx, USV_SLAB_STATE + 3, true}, {b.vy, USV_SLAB_STATE + 4, true}, {b.wz, USV_SLAB_STATE + 5, true},
-      {b.fl, USV_SLAB_STATE + 6, true}, {b.fr, USV_SLAB_STATE + 7, true}, {b.mass, USV_SLAB_PARAMS, true},
-      {b.com_x, USV_SLAB_PARAMS + 1, true}, {b.com_y, USV_SLAB_PARAMS + 2, true}, {b.com_z, USV_SLAB_PARAMS + 3, true},
-      {b.k_drag, USV_SLAB_PARAMS + 4, true}, {b.thr_l, USV_SLAB_PARAMS + 5, true}, {b.thr_r, USV_SLAB_PARAMS + 6, true},
-      {b.k_iz, USV_SLAB_PARAMS + 7, true}, {b.lin_damp, USV_SLAB_LIN_DAMP, false},
-      {b.quad_damp, USV_SLAB_QUAD_DAMP, false}, {b.tgt_x, USV_SLAB_TGT, true}, {b.tgt_y, USV_SLAB_TGT + 1, true},
-      {b.obst, USV_SLAB_OBST, true}, {b.prev_cmd, USV_SLAB_PREV_CMD, true}, {b.prev_dist, USV_SLAB_HIST, true},
-      {b.prev_head, USV_SLAB_HIST + 1, true}, {b.prev_pot, USV_SLAB_HIST + 2, true},
-      {b.prev_wz, USV_SLAB_HIST + 3, true}, {b.goal_cnt, USV_SLAB_IBUF, true}, {b.progress, USV_SLAB_IBUF + 1, true},
-      {b.reset_buf, USV_SLAB_IBUF + 2, true}, {b.done_succ, USV_SLAB_IBUF + 3, true},
-      {b.done_coll, USV_SLAB_IBUF + 4, true}, {b.just_reset, USV_SLAB_JUST_RESET, true},
-      {c.stats_on ? b.stats : nullptr, USV_SLAB_STATS, c.stats_on != 0}, {b.obs, USV_SLAB_OBS, true},
-      {b.rew, USV_SLAB_REW, true}, {b.dones, USV_SLAB_DONES, true}, {b.dist, USV_SLAB_DIST, false},
-      {b.dist ? b.env_org : nullptr, USV_SLAB_ENV_ORG, false},
-      {c.stale_root ? b.stale : nullptr, USV_SLAB_STALE, c.stale_root != 0}};
-  for (const Row &r : rows) {
-    if (!r.p) {
-      if (r.required) return -1;
+  for (const StepArr &a : step_arrays(c, b)) {
+    if (!a.p) {
+      if (a.required) return -1;
       continue;
     }
-    if (reinterpret_cast<const char *>(r.p) != base + (size_t)r.row * rb) return -1;
+    if (reinterpret_cast<const char *>(a.p) != base + (size_t)a.row * rb) return -1;
   }
   return sh;
+}
+
+// k_env_step_task<kind, stats on, injected uniforms>; nullptr for a kind it does not carry
+using TaskKern = void (*)(StepCfg, usv_bufs_t, const float *, const float *, float, uint64_t, uint64_t, const float *);
+template <int kKind>
+TaskKern task_kern_of(bool st, bool ij) {
+  return st ? (ij ? k_env_step_task<kKind, true, true> : k_env_step_task<kKind, true, false>)
+            : (ij ? k_env_step_task<kKind, false, true> : k_env_step_task<kKind, false, false>);
+}
+TaskKern task_kern(int kind, bool st, bool ij) {
+  switch (kind) {
+    case USV_TASK_GO_TO_POSE: return task_kern_of<USV_TASK_GO_TO_POSE>(st, ij);
+    case USV_TASK_TRACK_XYO: return task_kern_of<USV_TASK_TRACK_XYO>(st, ij);
+    case USV_TASK_GO_TO_XY: return task_kern_of<USV_TASK_GO_TO_XY>(st, ij);
+    case USV_TASK_KEEP_XY: return task_kern_of<USV_TASK_KEEP_XY>(st, ij);
+    case USV_TASK_TRACK_XY: return task_kern_of<USV_TASK_TRACK_XY>(st, ij);
+    default: return nullptr;
+  }
 }
 
 // any per-substep disturbance term on (then usv_bufs_t.dist must be set)
@@ -2007,31 +2023,15 @@ int usv_env_step_part(const usv_cfg_t *cfg, const usv_bufs_t *b, const float *ac
     const StepK k = step_constants(*cfg);
     const int grid = (b->n + kBlock - 1) / kBlock;
     hipStream_t s = (hipStream_t)stream;
-    const bool st = cfg->stats_on != 0, ij = u_inject != nullptr;
-    if (cfg->task_kind == USV_TASK_GO_TO_POSE) {
-      auto kern = st ? (ij ? k_env_step_task<USV_TASK_GO_TO_POSE, true, true> : k_env_step_task<USV_TASK_GO_TO_POSE, true, false>)
-                     : (ij ? k_env_step_task<USV_TASK_GO_TO_POSE, false, true> : k_env_step_task<USV_TASK_GO_TO_POSE, false, false>);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, s, StepCfg{*cfg, k}, *b, actions, lut_dev, action_bias, seed,
-                         step, u_inject);
-    } else if (cfg->task_kind == USV_TASK_TRACK_XYO) {
-      auto kern = st ? (ij ? k_env_step_task<USV_TASK_TRACK_XYO, true, true> : k_env_step_task<USV_TASK_TRACK_XYO, true, false>)
-                     : (ij ? k_env_step_task<USV_TASK_TRACK_XYO, false, true> : k_env_step_task<USV_TASK_TRACK_XYO, false, false>);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, s, StepCfg{*cfg, k}, *b, actions, lut_dev, action_bias, seed,
-                         step, u_inject);
+    const bool st = cfg->stats_on != 0;
+    const TaskKern kern = task_kern(kind, st, u_inject != nullptr);
+    if (!kern) return 1;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, s, StepCfg{*cfg, k}, *b, actions, lut_dev, action_bias, seed,
+                       step, u_inject);
+    if (kind == USV_TASK_TRACK_XYO) {
       USV_CHECK_LAUNCH();
       hipLaunchKernelGGL(st ? k_track_finish<true> : k_track_finish<false>, dim3(grid), dim3(kBlock), 0, s, *cfg, *b,
                          grid);
-    } else if (kind == USV_TASK_GO_TO_XY || kind == USV_TASK_KEEP_XY || kind == USV_TASK_TRACK_XY) {
-#define USV_TASK_KERN(KIND)                                                                                       \
-  (st ? (ij ? k_env_step_task<KIND, true, true> : k_env_step_task<KIND, true, false>)                               \
-      : (ij ? k_env_step_task<KIND, false, true> : k_env_step_task<KIND, false, false>))
-      auto kern = kind == USV_TASK_GO_TO_XY ? USV_TASK_KERN(USV_TASK_GO_TO_XY)
-                  : kind == USV_TASK_KEEP_XY ? USV_TASK_KERN(USV_TASK_KEEP_XY) : USV_TASK_KERN(USV_TASK_TRACK_XY);
-#undef USV_TASK_KERN
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, s, StepCfg{*cfg, k}, *b, actions, lut_dev, action_bias, seed,
-                         step, u_inject);
-    } else {
-      return 1;
     }
     USV_CHECK_LAUNCH();
     return 0;

@@ -6,10 +6,13 @@ branches) against the reference's recorded episodes X / K / V and against tests/
   own-trig leg's reward recorded);
 * in-kernel draws at n = 1, 33, 1000 against the restatement on the device's own states;
 * the shared path (integrator, DR, spawns, targets, reset masks) bit for bit across kinds;
-* penalize_action_variation on GoToPose; two trainers' epochs per new task, graph replay = eager.
+* penalize_action_variation on GoToPose; two trainers' epochs per new task, graph replay = eager;
+* k_env_step (CaptureXY) against k_env_step_task<GO_TO_XY> on the same inputs: the step they share, bit for bit.
 """
 import copy
+import ctypes
 import json
+import os
 
 import numpy as np
 import pytest
@@ -19,7 +22,7 @@ torch = pytest.importorskip("torch")
 from omniisaacgymenvs_loop_amd.tasks.usv_config import stat_names
 from tests import errtab as ET
 from tests import task_restate as R
-from tests.test_tasks_cpu import FIXTURE, _yaml
+from tests.test_tasks_cpu import CFG, FIXTURE, _yaml
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -215,6 +218,75 @@ def test_action_variation_penalty_on_go_to_pose():
         ET.check("actv_GoToPose", "sum", t_on.stats[slot].cpu().numpy(), acc, 1e-5, 1e-5, None, f"t={t}")
         np.testing.assert_array_equal(rews[2], rews[3], err_msg=f"aliased t={t}")
         np.testing.assert_array_equal(t_on.state.cpu().numpy(), t_off.state.cpu().numpy())
+
+
+def _capture_and_xy_cfgs(dist_on):
+    """CaptureXY's test config (quiet) and the same config carrying GoToXY's task and reward blocks: every
+    constant of the shared path (dynamics, DR, action processing, observation frame, privileged tail) is one."""
+    from omniisaacgymenvs_loop_amd.tasks.usv_config import load_yaml
+    cap = _quiet(load_yaml(os.path.join(CFG, "IROS2024", "USV_Virtual_CaptureXY_SysID-TEST.yaml")), ep_len=1000)
+    if dist_on:
+        d = cap["env"]["disturbances"]
+        for key in ("use_force_disturbance", "use_constant_force", "use_sinusoidal_force"):
+            d["forces"][key] = True
+        for key in ("use_torque_disturbance", "use_constant_torque", "use_sinusoidal_torque"):
+            d["torques"][key] = True
+        cap["env"]["water_current"] = {"use_water_current": True, "flow_velocity": [-0.2, 0.35, 0.0]}
+    xy, own = copy.deepcopy(cap), _yaml("GoToXY")
+    xy["env"]["task_parameters"] = own["env"]["task_parameters"]
+    xy["env"]["reward_parameters"] = own["env"].get("reward_parameters", {}) or {}
+    return cap, xy
+
+
+@pytest.mark.parametrize("n,dist_on", [(33, False), (33, True), (2048, False)], ids=["33", "33-dist", "2048"])
+def test_capture_and_task_kernels_share_one_step(n, dist_on):
+    """k_env_step (CaptureXY) and k_env_step_task<GO_TO_XY> on the same inputs, through usv_env_step itself: the
+    state rows, observation columns 0-2, the previous-command columns (and their array) and the privileged tail
+    agree bit for bit over 12 steps.  Every step hands both kernels CaptureXY's state / params / damp / dist /
+    env_org, random finite stale rows and the same random just_reset mask (a quarter of the envs: the stale-root
+    first substep, the zeroed thrust), actions past the clip and a bias that is 0 on every third step.
+    n = 33: the packed slab (StepWin), a partial wave; with the disturbances on, kDist against has_dist;
+    n = 2048: the canonical slab (FixedWin<13>), 8 workgroups."""
+    from omniisaacgymenvs_loop_amd import _capi
+    from omniisaacgymenvs_loop_amd._abi import DEFINES
+    cap, xy = (_task(y, n, seed=17) for y in _capture_and_xy_cfgs(dist_on))
+    assert cap.cfg.task_kind == 0 and xy.cfg.task_kind == DEFINES["USV_TASK_GO_TO_XY"]
+    assert cap.cfg.stale_root == 1 and (cap.dist is not None) == dist_on and (xy.dist is not None) == dist_on
+    assert bool(cap.cfg.fsin_on and cap.cfg.tsin_on and cap.cfg.current_on) == dist_on
+    rng = np.random.default_rng(40 + n)
+    first = torch.tensor(rng.uniform(-1, 1, (n, 2)).astype(np.float32), device=DEV)
+    bufs = []
+    for task in (cap, xy):
+        task.env_step(first)
+        b = task._make_bufs()
+        b.clock = None   # the step index and the bias are the arguments' (not the device clock's)
+        bufs.append(b)
+    pa, priv = DEFINES["USV_NOBS_BASE"] - 2, int(cap.cfg.priv_dim)
+    shared = ("state", "params", "damp", "dist", "env_org", "stale")
+    for t in range(12):
+        cap.stale.copy_(torch.tensor(rng.normal(0, 1, tuple(cap.stale.shape)).astype(np.float32)))
+        mask = torch.tensor((rng.random(n) < 0.25).astype(np.uint8), device=DEV)
+        assert 0 < int(mask.sum()) < n
+        for key in shared:
+            if getattr(cap, key) is not None:
+                getattr(xy, key).copy_(getattr(cap, key))
+        act = torch.tensor(rng.uniform(-1.2, 1.2, (n, 2)).astype(np.float32), device=DEV)
+        bias = 0.0 if t % 3 == 0 else 0.05 * t
+        for task, b in zip((cap, xy), bufs):
+            task.just_reset.copy_(mask)
+            _capi.call("usv_env_step", _capi.byref(task.cfg), _capi.byref(b), _capi.ptr(act), _capi.ptr(task.lut),
+                       ctypes.c_float(bias), 17, 100 + t, None, _capi.stream_ptr())
+        torch.cuda.synchronize()
+        oc, ox = cap.obs_buf_t.cpu().numpy(), xy.obs_buf_t.cpu().numpy()
+        for what, a, b in (("state", cap.state, xy.state), ("prev_cmd", cap.prev_cmd, xy.prev_cmd),
+                           ("obs 0-2", oc[:, :3], ox[:, :3]), ("obs prev_cmd", oc[:, pa:pa + 2], ox[:, pa:pa + 2]),
+                           ("priv tail", oc[:, pa + 2:pa + 2 + priv], ox[:, pa + 2:pa + 2 + priv])):
+            a, b = (v.cpu().numpy() if torch.is_tensor(v) else v for v in (a, b))
+            assert np.isfinite(a).all(), f"{what} t={t}"
+            np.testing.assert_array_equal(a, b, err_msg=f"{what} t={t}")
+        assert np.abs(oc[:, pa:pa + 2][mask.cpu().numpy() != 0]).max() == 0   # a reset env's previous command
+    assert float(cap.state[6:8].abs().max()) > 0 and float(cap.state[0:6].abs().max()) > 0
+    assert not dist_on or float(cap.dist.abs().max()) > 0   # drawn disturbance parameters
 
 
 def _agent_env(task_name, n, minibatch, use_graph, seed=11):
