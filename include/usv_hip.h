@@ -623,6 +623,72 @@ int usv_eval_step(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_eval_t *e
 int usv_eval_summary(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_eval_t *ev, double *out, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Fixed-horizon success-rate evaluation of the kinds without obstacles      */
+/* (omniisaacgymenvs/utils/eval_metrics.py: build_distance_dataframe :16-35, */
+/* check_stay :38-54, the time-under shares :83-91), streamed per env        */
+/* ------------------------------------------------------------------------ */
+#define USV_TEV_CH      2   /* error channels of a kind at the most */
+#define USV_TEV_LEVELS  3   /* time-under levels per channel */
+/* rows of usv_teval_t.table ([USV_TEV_ROWS][n] doubles, updated in place; integers held exactly).
+ * Per channel c, at USV_TEV_CH_STRIDE * c: */
+#define USV_TEV_FIRST_THR   0   /* smallest trace index with x < thr, -1 = never */
+#define USV_TEV_FIRST_THR2  1   /* the same with float32(thr / 2) */
+#define USV_TEV_STAY        2   /* 0 / 1: every x < float32(thr * 7.5) from max(FIRST_THR, 0) on */
+#define USV_TEV_UNDER0      3   /* steps with x < level[c][0], [1], [2] */
+#define USV_TEV_UNDER1      4
+#define USV_TEV_UNDER2      5
+#define USV_TEV_ERR_SUM     6   /* double sum of the float32 errors */
+#define USV_TEV_ERR_LAST    7
+#define USV_TEV_CH_STRIDE   8
+/* common, after the channels: */
+#define USV_TEV_STEPS      16   /* usv_teval_step calls since usv_teval_begin, the ones past horizon included */
+#define USV_TEV_RETURN     17   /* double sum of usv_bufs_t.rew over the horizon */
+#define USV_TEV_RESETS     18   /* steps of the horizon with reset_buf != 0 */
+#define USV_TEV_ROWS       19
+
+/* usv_teval_summary's output ([USV_TEVS_N] doubles) */
+#define USV_TEVS_ENVS        0
+#define USV_TEVS_CHANNELS    1
+#define USV_TEVS_STEPS_MIN   2   /* USV_TEV_STEPS: smallest and largest over the envs */
+#define USV_TEVS_STEPS_MAX   3
+#define USV_TEVS_RESETS      4   /* USV_TEV_RESETS total */
+#define USV_TEVS_RESET_ENVS  5   /* envs with USV_TEV_RESETS > 0 */
+#define USV_TEVS_CH          6   /* per channel c, at USV_TEVS_CH + USV_TEVS_CH_STRIDE * c (an unused channel: 0): */
+#define USV_TEVS_N_THR       0   /*   envs with FIRST_THR > -1 */
+#define USV_TEVS_N_THR2      1   /*   envs with FIRST_THR2 > -1 */
+#define USV_TEVS_N_STAY      2   /*   envs with STAY */
+#define USV_TEVS_UNDER       3   /*   3 totals of UNDER0..2 */
+#define USV_TEVS_ERR_SUM     6   /*   total of ERR_SUM */
+#define USV_TEVS_CH_STRIDE   7
+#define USV_TEVS_RETURN     20   /* count, mean, population standard deviation of USV_TEV_RETURN */
+#define USV_TEVS_N          23
+
+typedef struct usv_teval {
+  double *table;                               /* [USV_TEV_ROWS][n] */
+  float   thr[USV_TEV_CH];                     /* success threshold per channel (float32: what the comparison sees) */
+  float   level[USV_TEV_CH][USV_TEV_LEVELS];   /* time-under levels per channel */
+  int     horizon;                             /* evaluated steps */
+} usv_teval_t;
+
+/* The channels of a kind, from the task columns of the observation row (column 3 + k is task column k):
+ *   GoToXY, KeepXY       0: obs[5] (m)
+ *   GoToPose             0: obs[5] (m)                  1: |atan2(obs[7], obs[6])| (rad)
+ *   TrackXYVelocity      0: norm(obs[3], obs[4]) (m/s)
+ *   TrackXYOVelocity     0: norm(obs[3], obs[4]) (m/s)  1: |obs[5]| (rad/s)
+ * Returns 1 or 2; 0 for CaptureXY (and for a NULL cfg). */
+int usv_teval_channels(const usv_cfg_t *cfg);
+/* Status 1: a NULL argument, table, env buffer (obs, rew, reset_buf) or output, n <= 0; status 2: horizon < 1, or
+ * a threshold or level of a used channel that is not finite and positive; status 3: CaptureXY (usv_eval_* is the
+ * tool for it).  All checks precede device work.  One thread per env, no atomics. */
+/* FIRST_* = -1, STAY = 1, every other row 0 */
+int usv_teval_begin(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_teval_t *tev, void *stream);
+/* after usv_env_step: trace index = STEPS before the increment.  A step past horizon is counted in STEPS and
+ * otherwise ignored.  Resets inside the horizon are counted, not acted on: the trace runs on. */
+int usv_teval_step(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_teval_t *tev, void *stream);
+/* out [USV_TEVS_N] (device): one workgroup, doubles in a fixed order: the same table gives the same bits */
+int usv_teval_summary(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_teval_t *tev, double *out, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Scenario tables (scripts/build_usv_scenario_table.py: sampling :153-209,  */
 /* metrics :215-258; scripts/teacher_filter_scenario_table.py: the           */
 /* per-scenario aggregate :712-759 and the filter's verdict :512-552)        */

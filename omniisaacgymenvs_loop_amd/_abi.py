@@ -60,13 +60,13 @@ def _struct_fields(txt: str, name: str, defines: dict):
             item = item.strip()
             ptr = item.startswith("*")
             item = item.lstrip("*").strip()
-            am = re.match(r"(\w+)\s*(?:\[(.+)\])?", item)
-            fname, arr = am.group(1), am.group(2)
+            am = re.match(r"(\w+)\s*((?:\[[^\]]+\]\s*)*)$", item)
+            fname, dims = am.group(1), re.findall(r"\[([^\]]+)\]", am.group(2))
             if ptr:
                 ct = ctypes.c_void_p
             else:
                 ct = _CTYPES[base]
-            if arr is not None:
+            for arr in reversed(dims):   # a[A][B]: A arrays of B
                 ct = ct * int(eval(arr, {}, defines))
             fields.append((fname, ct))
     return fields
@@ -90,6 +90,10 @@ class UsvHydro(ctypes.Structure):
 
 class UsvEval(ctypes.Structure):
     _fields_ = _struct_fields(_TXT, "usv_eval", DEFINES)
+
+
+class UsvTEval(ctypes.Structure):
+    _fields_ = _struct_fields(_TXT, "usv_teval", DEFINES)
 
 
 class LzCfg(ctypes.Structure):
@@ -135,10 +139,12 @@ PEN = enum_values("usv_pen_kind")
 # usv_hip_layout_key(); _capi.lib() refuses a library whose key differs from layout_key() here, so a
 # library built from another header -- a moved slab row, a resized buffer, a reordered struct --
 # fails loudly before its first call instead of addressing past a buffer.
-LAYOUT_STRUCTS = ("usv_cfg", "usv_bufs", "usv_hydro", "usv_eval", "ppo_cfg", "ppo_adam_banks", "ppo_dp", "lz_cfg")
+LAYOUT_STRUCTS = ("usv_cfg", "usv_bufs", "usv_hydro", "usv_eval", "usv_teval", "ppo_cfg", "ppo_adam_banks", "ppo_dp",
+                  "lz_cfg")
 LAYOUT_ENUMS = ("usv_stat_key", "usv_pen_kind", "usv_dist_row")
 _STRUCT_CLASSES = {"usv_cfg": UsvCfg, "usv_bufs": UsvBufs, "usv_hydro": UsvHydro, "usv_eval": UsvEval,
-                   "ppo_cfg": PpoCfg, "ppo_adam_banks": PpoAdamBanks, "ppo_dp": PpoDp, "lz_cfg": LzCfg}
+                   "usv_teval": UsvTEval, "ppo_cfg": PpoCfg, "ppo_adam_banks": PpoAdamBanks, "ppo_dp": PpoDp,
+                   "lz_cfg": LzCfg}
 GUARD_DEFINES = ("USV_HIP_H",)
 
 

@@ -13,7 +13,7 @@ import subprocess
 
 import torch  # noqa: F401  -- load torch's HIP runtime first; the .so binds to it (same SONAME)
 
-from ._abi import PpoCfg, UsvBufs, UsvCfg, UsvEval
+from ._abi import PpoCfg, UsvBufs, UsvCfg, UsvEval, UsvTEval
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -21,9 +21,9 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libusv_hip.so")
 # instrumented build (per-workgroup phase timestamps, tools/phase_probe.py); selected with USV_HIP_PROBE=1
 PROBE_LIB_PATH = os.path.join(LIB_DIR, "libusv_hip_probe.so")
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("usv_env.hip", "usv_field.hip", "usv_eval.hip", "ppo.hip", "loopz.hip",
-                                                    "usv_sysid.hip", "usv_scenario.hip", "usv_compare.hip",
-                                                    "usv_analysis.hip")]
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("usv_env.hip", "usv_field.hip", "usv_eval.hip", "usv_task_eval.hip",
+                                                    "ppo.hip", "loopz.hip", "usv_sysid.hip", "usv_scenario.hip",
+                                                    "usv_compare.hip", "usv_analysis.hip")]
 DEPS = SOURCES + [os.path.join(HERE, "csrc", "usv_device.h"), os.path.join(HERE, "csrc", "usv_layout_gen.h"),
                   os.path.join(ROOT, "include", "usv_hip.h")]
 
@@ -70,6 +70,10 @@ def _declare(lib):
         "usv_eval_mark": [P, P, P, P],
         "usv_eval_step": [P, P, P, P, P],
         "usv_eval_summary": [P, P, P, P, P],
+        "usv_teval_channels": [P],
+        "usv_teval_begin": [P, P, P, P],
+        "usv_teval_step": [P, P, P, P],
+        "usv_teval_summary": [P, P, P, P, P],
         "usv_scn_generate": [U64, I64, I, D, D, D, D, D, I, I, P, P, P],
         "usv_scn_metrics": [P, I, D, D, P, P],
         "usv_scn_fold": [P, I, I, I, I, D, I, D, I, P, P],
@@ -183,4 +187,5 @@ def byref(s):
     return ctypes.byref(s)
 
 
-__all__ = ["build", "lib", "call", "call_rc", "ptr", "stream_ptr", "byref", "UsvCfg", "UsvBufs", "UsvEval", "PpoCfg", "LIB_PATH"]
+__all__ = ["build", "lib", "call", "call_rc", "ptr", "stream_ptr", "byref", "UsvCfg", "UsvBufs", "UsvEval", "UsvTEval",
+           "PpoCfg", "LIB_PATH"]

@@ -177,6 +177,36 @@
   X(USV_EVS_METRICS, "USV_EVS_METRICS") \
   X(USV_EVS_NMETRIC, "USV_EVS_NMETRIC") \
   X(USV_EVS_N, "USV_EVS_N") \
+  X(USV_TEV_CH, "USV_TEV_CH") \
+  X(USV_TEV_LEVELS, "USV_TEV_LEVELS") \
+  X(USV_TEV_FIRST_THR, "USV_TEV_FIRST_THR") \
+  X(USV_TEV_FIRST_THR2, "USV_TEV_FIRST_THR2") \
+  X(USV_TEV_STAY, "USV_TEV_STAY") \
+  X(USV_TEV_UNDER0, "USV_TEV_UNDER0") \
+  X(USV_TEV_UNDER1, "USV_TEV_UNDER1") \
+  X(USV_TEV_UNDER2, "USV_TEV_UNDER2") \
+  X(USV_TEV_ERR_SUM, "USV_TEV_ERR_SUM") \
+  X(USV_TEV_ERR_LAST, "USV_TEV_ERR_LAST") \
+  X(USV_TEV_CH_STRIDE, "USV_TEV_CH_STRIDE") \
+  X(USV_TEV_STEPS, "USV_TEV_STEPS") \
+  X(USV_TEV_RETURN, "USV_TEV_RETURN") \
+  X(USV_TEV_RESETS, "USV_TEV_RESETS") \
+  X(USV_TEV_ROWS, "USV_TEV_ROWS") \
+  X(USV_TEVS_ENVS, "USV_TEVS_ENVS") \
+  X(USV_TEVS_CHANNELS, "USV_TEVS_CHANNELS") \
+  X(USV_TEVS_STEPS_MIN, "USV_TEVS_STEPS_MIN") \
+  X(USV_TEVS_STEPS_MAX, "USV_TEVS_STEPS_MAX") \
+  X(USV_TEVS_RESETS, "USV_TEVS_RESETS") \
+  X(USV_TEVS_RESET_ENVS, "USV_TEVS_RESET_ENVS") \
+  X(USV_TEVS_CH, "USV_TEVS_CH") \
+  X(USV_TEVS_N_THR, "USV_TEVS_N_THR") \
+  X(USV_TEVS_N_THR2, "USV_TEVS_N_THR2") \
+  X(USV_TEVS_N_STAY, "USV_TEVS_N_STAY") \
+  X(USV_TEVS_UNDER, "USV_TEVS_UNDER") \
+  X(USV_TEVS_ERR_SUM, "USV_TEVS_ERR_SUM") \
+  X(USV_TEVS_CH_STRIDE, "USV_TEVS_CH_STRIDE") \
+  X(USV_TEVS_RETURN, "USV_TEVS_RETURN") \
+  X(USV_TEVS_N, "USV_TEVS_N") \
   X(USV_SCN_SITE_POSE, "USV_SCN_SITE_POSE") \
   X(USV_SCN_SITE_YAW, "USV_SCN_SITE_YAW") \
   X(USV_SCN_SITE_OBST, "USV_SCN_SITE_OBST") \
@@ -577,6 +607,11 @@
   X(offsetof(usv_eval_t, max_episodes), "usv_eval.max_episodes") \
   X(offsetof(usv_eval_t, action_scale), "usv_eval.action_scale") \
   X(offsetof(usv_eval_t, control_dt), "usv_eval.control_dt") \
+  X(sizeof(usv_teval_t), "sizeof usv_teval") \
+  X(offsetof(usv_teval_t, table), "usv_teval.table") \
+  X(offsetof(usv_teval_t, thr), "usv_teval.thr") \
+  X(offsetof(usv_teval_t, level), "usv_teval.level") \
+  X(offsetof(usv_teval_t, horizon), "usv_teval.horizon") \
   X(sizeof(ppo_cfg_t), "sizeof ppo_cfg") \
   X(offsetof(ppo_cfg_t, horizon), "ppo_cfg.horizon") \
   X(offsetof(ppo_cfg_t, n_envs), "ppo_cfg.n_envs") \

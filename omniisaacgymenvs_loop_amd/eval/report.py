@@ -144,3 +144,103 @@ def write_summary_json(path: str, s: Dict[str, Any]) -> None:
     with open(path, "w") as f:
         json.dump(clean(s), f, indent=2, allow_nan=False)
         f.write("\n")
+
+
+# ---- fixed-horizon success-rate evaluation (usv_teval_*, eval.task_evaluator) -------------------------------
+# the reference's tables (utils/eval_metrics.py): group key -> unit suffix of its column names, and the prefix of
+# the time-under rows (its PT5 / PT2 / PT1 and OT5 / OT2 / OT1 are position and heading; the others in that style)
+TASK_UNITS = {"position": "m", "heading": "rad", "xy_velocity": "m/s", "omega_velocity": "rad/s"}
+TASK_TIME_UNDER_PREFIX = {"position": "PT", "heading": "OT", "xy_velocity": "VT", "omega_velocity": "WT"}
+TASK_CHANNEL_FIELDS = ("first_thr", "first_thr2", "stay", "under0", "under1", "under2", "err_mean", "err_last")
+
+
+def task_column_names(channel: str, thr: float) -> tuple:
+    """The reference's three column names for a channel at threshold thr (a Python float, formatted as it does)."""
+    u = TASK_UNITS[channel]
+    return (f"success_rate_{thr}_{u}", f"success_rate_{thr / 2}_{u}", f"success_and_stay_within_{thr * 7.5}_{u}")
+
+
+def task_csv_columns(channels) -> tuple:
+    return ("env", "steps", "return_raw", "resets") + tuple(f"{c}_{f}" for c in channels for f in TASK_CHANNEL_FIELDS)
+
+
+def task_records_from_table(table: np.ndarray, channels, horizon: int) -> Dict[str, np.ndarray]:
+    """The device table ([USV_TEV_ROWS][n] doubles) as per-env arrays."""
+    n = table.shape[1]
+    steps = table[DEFINES["USV_TEV_STEPS"]].astype(np.int64)
+    out = {"env": np.arange(n, dtype=np.int32), "steps": steps,
+           "return_raw": table[DEFINES["USV_TEV_RETURN"]].copy(),
+           "resets": table[DEFINES["USV_TEV_RESETS"]].astype(np.int64)}
+    seen = np.maximum(np.minimum(steps, int(horizon)), 1)
+    for c, name in enumerate(channels):
+        r = table[DEFINES["USV_TEV_CH_STRIDE"] * c:DEFINES["USV_TEV_CH_STRIDE"] * (c + 1)]
+        out[f"{name}_first_thr"] = r[DEFINES["USV_TEV_FIRST_THR"]].astype(np.int64)
+        out[f"{name}_first_thr2"] = r[DEFINES["USV_TEV_FIRST_THR2"]].astype(np.int64)
+        out[f"{name}_stay"] = r[DEFINES["USV_TEV_STAY"]].astype(np.int32)
+        for l in range(DEFINES["USV_TEV_LEVELS"]):
+            out[f"{name}_under{l}"] = r[DEFINES["USV_TEV_UNDER0"] + l].astype(np.int64)
+        out[f"{name}_err_mean"] = r[DEFINES["USV_TEV_ERR_SUM"]] / seen
+        out[f"{name}_err_last"] = r[DEFINES["USV_TEV_ERR_LAST"]].copy()
+    return out
+
+
+def write_task_csv(path: str, records: Dict[str, np.ndarray], channels) -> int:
+    """One row per env, task_csv_columns order; returns the row count."""
+    cols = task_csv_columns(channels)
+    rows = int(records["env"].shape[0])
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(cols)
+        for i in range(rows):
+            w.writerow([_fmt(records[k][i]) for k in cols])
+    return rows
+
+
+def task_summary_from_device(out: np.ndarray, channels, thresholds, thresholds_f32, levels,
+                             horizon: int) -> Dict[str, Any]:
+    """usv_teval_summary's [USV_TEVS_N] doubles as the reference's tables: per channel group key a "table" with
+    its three column names (percentages: mean(first_thr > -1) * 100, the same for thr / 2, mean(stay) * 100) and
+    the "time_under" percentages of all (step, env) pairs.  thresholds: as given (they name the columns);
+    thresholds_f32: what the device compared with."""
+    envs = int(out[DEFINES["USV_TEVS_ENVS"]])
+    smin, smax = int(out[DEFINES["USV_TEVS_STEPS_MIN"]]), int(out[DEFINES["USV_TEVS_STEPS_MAX"]])
+    s: Dict[str, Any] = {"envs": envs, "channels": list(channels), "horizon": int(horizon), "steps_min": smin,
+                         "steps_max": smax, "resets": int(out[DEFINES["USV_TEVS_RESETS"]]),
+                         "envs_reset": int(out[DEFINES["USV_TEVS_RESET_ENVS"]])}
+    r0 = DEFINES["USV_TEVS_RETURN"]
+    s["return_raw"] = _with_ci(int(out[r0]), out[r0 + 1], out[r0 + 2])
+    pairs = float(max(min(smin, int(horizon)), 1) * max(envs, 1))
+    for c, name in enumerate(channels):
+        o = out[DEFINES["USV_TEVS_CH"] + DEFINES["USV_TEVS_CH_STRIDE"] * c:]
+        names = task_column_names(name, float(thresholds[c]))
+        rates = (o[DEFINES["USV_TEVS_N_THR"]] / envs * 100, o[DEFINES["USV_TEVS_N_THR2"]] / envs * 100,
+                 o[DEFINES["USV_TEVS_N_STAY"]] / envs * 100)
+        under = [float(o[DEFINES["USV_TEVS_UNDER"] + l]) for l in range(DEFINES["USV_TEV_LEVELS"])]
+        s[name] = {"threshold": float(thresholds[c]), "threshold_f32": float(thresholds_f32[c]),
+                   "levels": [float(v) for v in levels[c]],
+                   "table": {k: float(v) for k, v in zip(names, rates)},
+                   "time_under": {f"{TASK_TIME_UNDER_PREFIX[name]}_{float(lv):.6g}": u / pairs * 100
+                                  for lv, u in zip(levels[c], under)},
+                   "mean_error": float(o[DEFINES["USV_TEVS_ERR_SUM"]]) / pairs}
+    return s
+
+
+def format_task_summary(s: Dict[str, Any]) -> str:
+    """The reference's tables, one line per column, and a warning when the run was not fixed-horizon."""
+    lines = [f"[evaluate] envs={s['envs']} horizon={s['horizon']} steps={s['steps_min']}..{s['steps_max']}"]
+    for name in s["channels"]:
+        g = s[name]
+        lines.append(f"  {name}:")
+        lines += [f"    {k}: {v:.4f}" for k, v in g["table"].items()]
+        lines.append("    percentage of time spent under (" + ", ".join(f"{lv:.6g}" for lv in g["levels"]) + f") "
+                     f"{TASK_UNITS[name]}: " + " ".join(f"{k}={v:.4f}" for k, v in g["time_under"].items()))
+    m = s["return_raw"]
+    lines.append(f"  return_raw: mean={m['mean']:.6g} std={m['std']:.6g} "
+                 f"95%CI=[{m['ci95_lo']:.6g}, {m['ci95_hi']:.6g}]")
+    if s["resets"] > 0:
+        lines.append(f"[evaluate] WARNING: {s['envs_reset']} env(s) were reset inside the horizon ({s['resets']} "
+                     "resets): the traces run on across them; set task.env.fixed_horizon_eval=True and "
+                     "task.env.maxEpisodeLength >= horizon + 2")
+    if s["steps_min"] < s["horizon"]:
+        lines.append(f"[evaluate] WARNING: only {s['steps_min']} of {s['horizon']} steps were evaluated")
+    return "\n".join(lines)

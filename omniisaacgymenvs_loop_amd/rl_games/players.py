@@ -89,6 +89,20 @@ class PpoPlayerContinuous:
         self.evaluator = ev
         return ev.episodes(), ev.summary()
 
+    def evaluate_horizon(self, horizon: int = 500, thresholds=None, levels=None):
+        """Play deterministically for exactly `horizon` env steps on a task without obstacles, with the streaming
+        success metrics of every env kept on the device (eval.TaskTraceEvaluator: first time under a threshold,
+        reached-and-stayed, time under three levels; thresholds default to the task's own tolerances); returns
+        (records: dict of per-env numpy arrays; summary: dict with the reference's tables).  No host sync inside
+        the loop.  The task should run with fixed_horizon_eval on and maxEpisodeLength >= horizon + 2
+        (scripts/evaluate_policy.py sets both); resets inside the horizon are counted in the summary."""
+        from ..eval import TaskTraceEvaluator, rollout_horizon
+        task = self.env._task
+        ev = TaskTraceEvaluator(task, horizon, thresholds=thresholds, levels=levels)
+        rollout_horizon(task, lambda obs: self.get_action(obs, True), ev)
+        self.evaluator = ev
+        return ev.records(), ev.summary()
+
     def run(self):
         obs = self.env.reset()
         steps = torch.zeros(self.num_actors, device=self.device)
