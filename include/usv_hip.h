@@ -309,8 +309,8 @@ typedef struct usv_bufs {
   float   *extras_acc;             /* [ceil(n/256)][USV_NSTAT] reset-kernel per-workgroup sums (scratch) */
   float   *field_old_tgt;          /* [2][n] target used by the field of each reset env */
   float   *slot_stats;             /* [n][USV_FIELD_SLOT_STATS] per-reset-slot field statistics (scratch) */
-  float   *sdf;                    /* [n][USV_FIELD_STRIDE] raw cost-to-go of each env's field as the sweeps leave it,
-                                      row-major [150][150] (+inf unreachable): k_field_stats tiles it into .field */
+  float   *sdf;                    /* [n][USV_FIELD_STRIDE] scratch of the reference's 225 literal sweeps (an env whose
+                                      tile-sweep fixed point is not certified): row-major [150][150] cost-to-go */
   const float *grid_lin;           /* [150] cell centres of the field grid */
   float   *dist;                   /* [USV_NDIST][n] disturbance parameters; NULL when no disturbance is on */
   const float *env_org;            /* [2][n] world x, y of each env's origin (RLTask._env_pos); NULL = 0 */
@@ -364,7 +364,8 @@ typedef struct usv_bufs {
 #define USV_SC_GOAL     37    /* goal_pos x, y */
 #define USV_SCENE_STRIDE 40
 
-#define USV_FIELD_SLOT_STATS 192   /* 16 + 12 per 30-row band (5 bands), obstacles at 160 (32) */
+#define USV_FIELD_SLOT_STATS 192   /* 16 folded + two partial rows of 12 (the sweep kernel's cost row at 16,
+                                      k_field_near's at 28), obstacles at 160 (32) */
 
 /* control words */
 #define USV_CTL_RESET_COUNT 0

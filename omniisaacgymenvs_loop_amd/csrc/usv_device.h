@@ -217,7 +217,7 @@ __device__ __forceinline__ float grid_coord(const float *lin, float map_size, in
 }
 // compute_occupancy_and_sdf (d_multi_gemini.py:66-104) for one cell, ob(o) -> the centre of obstacle o: min
 // over the 16 obstacles of the squared distance (dx*dx rounded, then fma with dy), sqrt, minus the radius --
-// k_field_stats' separable SDF forms the same operations per cell, so the bits are the same.  Squared
+// k_field_near forms the same operations per cell over the obstacles in reach, so the bits are the same.  Squared
 // distances are >= 0: float order == u32 order (balanced min tree).
 template <class Ob>
 __device__ __forceinline__ float cell_sdf(Ob ob, float gx, float gy, float radius) {

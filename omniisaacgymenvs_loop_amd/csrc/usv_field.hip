@@ -11,7 +11,8 @@
 // persistent over the device-side reset count; _pack holds two envs per CU):
 //   1. occupancy of the 150x150 grid as a 2.8 KB bit map in LDS, splatted per
 //      obstacle over its bounding box with the exact per-cell distance test (the
-//      SDF itself is computed by k_field_stats, off this kernel's critical path);
+//      SDF itself is computed by k_field_near, off this kernel's critical path), and
+//      beside it the near map: the union of the obstacles' windows (near_window);
 //   2. cost-to-go: 225 threads each own a 10x10 tile in registers and relax it
 //      with a raster forward + backward chamfer sweep against a halo ring read
 //      from LDS; one barrier per iteration with a block-wide "changed" vote.
@@ -22,13 +23,18 @@
 //      r = 0.5 m obstacles is < 120; checked on the golden fixtures).  An
 //      occupied target cell is seeded exactly as the reference's first Jacobi
 //      sweep does (its neighbours get 1 / 1.414);
-//   3. raw cost into the env's field tiles (b.field: the threads' own 10 x 10 tiles).
-// k_field_stats (per slot and 30-row band): the SDF (recomputed from the obstacles)
-//   and the cost tiles -> per-env statistics, split by finite and infinite cost so that the batch
-//   constant inf_val (unknown until every env is done) enters only through one
-//   monotone scalar per batch.
-// k_field_batch (one workgroup): batch max of finite costs -> inf_val, the
-//   repulsion mask of infinite cells, batch J max, any-inside flag.
+//   3. raw cost into the env's field tiles (b.field: the threads' own 10 x 10 tiles);
+//   4. the slot's cost-only statistics from the registers the tile store uses: the finite-cost
+//      extrema, the any-infinite flag, and what the cells outside the near map give the J
+//      statistics (they have J = 0 and are not inside: only "some finite / some infinite
+//      cell lies out there" matters) -> the slot's cost partial row.
+// k_field_near (one workgroup per slot, a wave per obstacle window): the SDF (recomputed from
+//   the obstacles) and the gathered costs of the window cells -> the J statistics of the near
+//   cells and the inside flag, split by finite and infinite cost so that the batch constant
+//   inf_val (unknown until every env is done) enters only through one monotone scalar per
+//   batch -> the slot's near partial row.
+// k_field_batch: folds the two partial rows of every slot, then the batch max of finite costs
+//   -> inf_val, the repulsion mask of infinite cells, batch J max, any-inside flag.
 // k_field_norm (one thread per slot): the env's normalisation constants (b.fnorm); the field itself is
 //   never materialised -- readers form texels from the SDF, the cost and the constants (field_value).
 #include "usv_device.h"
@@ -44,9 +50,12 @@ constexpr int T = 10;            // tile edge
 constexpr int NT = G / T;        // 15 tiles per edge
 constexpr int kWaveThreads = 256;
 constexpr int kMaxIters = 4096;  // safety cap (never reached)
-constexpr int kSlotStride = USV_FIELD_SLOT_STATS;   // floats per reset slot: 16 final + 12 per chunk + obstacles
+constexpr int kSlotStride = USV_FIELD_SLOT_STATS;   // floats per reset slot: 16 final + 12 per partial row + obstacles
 constexpr int kSlotObst = 160;                      // the slot's 16 obstacle centres (x, y interleaved)
-static_assert(kSlotObst + 2 * USV_NOBST <= kSlotStride, "slot_stats layout");
+constexpr int kSlotCost = 16, kSlotNear = 28;      // the two partial rows: k_field_wave*'s and k_field_near's
+constexpr int kParts = 2;
+static_assert(kSlotObst + 2 * USV_NOBST <= kSlotStride && kSlotNear == kSlotCost + 12 &&
+              kSlotCost + 12 * kParts <= kSlotObst, "slot_stats layout");
 constexpr int kFieldPackMinEnvs = 32768;           // k_field_wave_pack (two envs per CU) from this many envs
 // USV_SWEEP_WAVES: waves per SIMD the packed sweep kernel is compiled for (2: two reset envs per CU at <= 256
 // VGPRs; 3: three envs per CU, 3 x 51.7 KB of LDS, <= 168 VGPRs) and its persistent grid (256 CUs x that)
@@ -87,11 +96,58 @@ __device__ __forceinline__ bool occ_bit(const uint32_t *occ, int r, int cc) {
   return (occ[cc * kOccColWords + (r >> 5)] >> (r & 31)) & 1u;
 }
 
+// Near and far cells.  The SDF enters the statistics only through j_raw (0 unless dist - 2 r_obs <
+// influence_radius) and the inside test (dist <= 2 r_obs): a cell whose squared distance to every obstacle is
+// >= far_d^2 has dte >= R + 1e-3 (jr = +0, not inside) whatever the rounding of the sqrt and the two
+// subtractions, and enters only through its cost.
+__device__ __forceinline__ float field_far_d(const usv_cfg_t &c, float cell) {
+  return c.influence_radius + 2.0f * c.obstacle_radius + 0.01f * cell + 1e-3f;
+}
+// An obstacle's window: the grid cells with |x - ox| <= far_d + cell and |y - oy| <= far_d + cell, as index
+// ranges clipped to the grid (empty: cl > ch; a parked obstacle at (999, 999) has none).  A cell outside it is
+// farther than far_d + cell (less the rounding of the index arithmetic, ~1e-5 cell) from the obstacle in x or
+// in y, so outside every window the far criterion holds with most of a cell to spare.  The sweep kernels
+// (near map) and k_field_near (the cells it visits) both call this with the same operands: the same windows.
+struct Win {
+  int cl, ch, rl, rh;
+};
+__device__ __forceinline__ Win near_window(float ox, float oy, float half_m, float cellf, float far_d) {
+  const float wc = (far_d + cellf) / cellf;
+  const float ic = (ox + half_m) / cellf - 0.5f, jc = (oy + half_m) / cellf - 0.5f;
+  Win w{1, 0, 1, 0};
+  if (!(fabsf(ic) < 4.0f * G && fabsf(jc) < 4.0f * G)) return w;
+  const int cl = max((int)ceilf(ic - wc), 0), ch = min((int)floorf(ic + wc), G - 1);
+  const int rl = max((int)ceilf(jc - wc), 0), rh = min((int)floorf(jc + wc), G - 1);
+  if (cl <= ch && rl <= rh) w = Win{cl, ch, rl, rh};
+  return w;
+}
+// rows [r0, r0 + kRows) of column cc of a column-major bit map (occ's layout) as the low bits of a word
+template <int kRows>
+__device__ __forceinline__ uint32_t col_bits(const uint32_t *map, int r0, int cc) {
+  static_assert(kRows <= 32, "one word of rows");
+  const int w = r0 >> 5;
+  const uint64_t lo = map[cc * kOccColWords + w], hi = map[cc * kOccColWords + min(w + 1, kOccColWords - 1)];
+  return (uint32_t)(((hi << 32) | lo) >> (r0 & 31)) & ((1u << kRows) - 1u);
+}
+// A cell's share of the slot's cost partial row, on bit patterns (costs are >= 0: u32 order is float order;
+// +inf and the occupied marker 0xFFFFFFFF both count as infinite; nm = all ones for a cell of the near map, else
+// 0).  gmin < kInfBits afterwards <=> some finite cell; amax >= kInfBits <=> some infinite cell; fmin / fmax the
+// same over the far cells only (a near cell is forced to all ones in the min and to 0 in the max).
+struct CostFold {
+  uint32_t gmin = 0xFFFFFFFFu, amax = 0u, fmin = 0xFFFFFFFFu, fmax = 0u;
+  __device__ __forceinline__ void cell(uint32_t hb, uint32_t nm) {
+    gmin = min(gmin, hb);
+    amax = max(amax, hb);
+    fmin = min(fmin, hb | nm);
+    fmax = max(fmax, hb & ~nm);
+  }
+};
+
 // compute_cost_field_wavefront (d_multi_gemini.py:135-192) as written: int(1.5 G) = 225
 // synchronous sweeps of min(self, 8 rolled neighbours + move cost) with the rolled-in edge at
 // +inf, occupied cells forced to +inf after every sweep, the target cell seeded with 0.  Run
 // only for an env whose tile-sweep fixed point is not certified equal to it (see below):
-// ping-pong through the env's field row (k_field_stats writes the SDF there later) and the
+// ping-pong through the env's field row and the
 // slot's scratch, where the result ends as k_field_wave leaves its raw cost, one block barrier per sweep; all waves of the block share the CU's L1, so plain
 // global loads see the other waves' stores after the barrier.
 constexpr int kRefSweeps = (G * 3) / 2;
@@ -148,8 +204,8 @@ __global__ __launch_bounds__(kPlaceTB) void k_field_place(usv_cfg_t c, usv_bufs_
   }
 }
 
-// LDS holds the tile edges and a 2.8 KB occupancy bit map (the SDF itself goes to
-// the per-slot HBM scratch only): 51 KB.  Two launch shapes of the same body:
+// LDS holds the tile edges, a 2.9 KB occupancy bit map and the near map of the same shape (the SDF
+// itself is never stored): 54 KB.  Two launch shapes of the same body:
 // k_field_wave_pack is held to 256 registers (its spills sit in the per-slot
 // prologue, not in the sweep), so two reset envs share a CU -- one wave of each per
 // SIMD -- for batches that fill the chip more than once; k_field_wave keeps the
@@ -170,6 +226,8 @@ __device__ __forceinline__ void field_wave_body(const usv_cfg_t &c, const usv_bu
   static_assert(G % TH == 0 && G % TW == 0 && NTR <= 16 && NTC <= 8 * WC && NTHR % 128 == 0, "sweep tiling");
   static_assert(USV_FIELD_TH == TH && USV_FIELD_TW % TW == 0, "sweep tiles inside the field tiles");
   __shared__ uint32_t occ[G * kOccColWords];
+  __shared__ uint32_t nearm[G * kOccColWords];   // the near map: union of the obstacles' windows (occ's layout)
+  __shared__ float cred[5][NTHR / 64];           // the waves' cost partial rows
   __shared__ float edgeh[2][NPR * NPC][TW];   // top / bottom row of every tile
   __shared__ float edgev[2][NPR * NPC][TH];   // left / right column
   __shared__ int lastc[NPR * NPC];
@@ -237,7 +295,7 @@ __device__ __forceinline__ void field_wave_body(const usv_cfg_t &c, const usv_bu
       so[tid] = b.obst[(size_t)tid * n + e];
     }
     if (tid < G) slin[tid] = grid_coord(b.grid_lin, c.map_size, tid);
-    for (int q = tid; q < G * kOccColWords; q += NTHR) occ[q] = 0u;
+    for (int q = tid; q < G * kOccColWords; q += NTHR) occ[q] = nearm[q] = 0u;
     __syncthreads();
 #ifdef USV_PHASE_PROBE
     if (tid == 0 && blockIdx.x < 4096) g_probe_field[blockIdx.x][12] = wall_clock64();
@@ -261,6 +319,17 @@ __device__ __forceinline__ void field_wave_body(const usv_cfg_t &c, const usv_bu
         const float dx = slin[cc] - ox, dy = slin[r] - oy;
         if (sqrtf(fmaf(dy, dy, dx * dx)) - c.obstacle_radius <= 0.f)
           atomicOr(&occ[cc * kOccColWords + (r >> 5)], 1u << (r & 31));
+      }
+      // the near map: every obstacle's window, thread (k, o) marks columns cl + k, cl + k + NTHR / 16, .. of
+      // obstacle o's (rows rl..rh of a column: one or two words)
+      static_assert((USV_NOBST & (USV_NOBST - 1)) == 0 && NTHR % USV_NOBST == 0, "near map threads");
+      const int o = tid & (USV_NOBST - 1);
+      const Win w = near_window(so[2 * o], so[2 * o + 1], half_m, cellf, field_far_d(c, cellf));
+      for (int cc = w.cl + tid / USV_NOBST; cc <= w.ch; cc += NTHR / USV_NOBST) {
+        for (int wi = w.rl >> 5; wi <= w.rh >> 5; ++wi) {
+          const int lo = max(w.rl, 32 * wi), hi = min(w.rh, 32 * wi + 31);
+          atomicOr(&nearm[cc * kOccColWords + wi], (uint32_t)(((1ull << (hi - lo + 1)) - 1ull) << (lo & 31)));
+        }
       }
     }
     __syncthreads();
@@ -409,21 +478,27 @@ __device__ __forceinline__ void field_wave_body(const usv_cfg_t &c, const usv_bu
     // whose fixed-point cost is <= kPinnedCost has an optimal path of <= 225 hops and the two agree.
     // If some finite cost exceeds it (long detours; never for the packaged spawn ranges, possible
     // for replayed scenes) or the sweep cap was reached, the env takes the reference's sweeps. ----
+    // The same pass folds the tile's share of the slot's cost partial row (CostFold), each column's near bits
+    // taken from the near map; hmax (>= 0) is the tile's largest finite cost whenever it has a finite cell.
     constexpr float kPinnedCost = 224.0f;
     float hmax = 0.f;
+    CostFold cf;
     if (tile_ok) {
 #pragma unroll
-      for (int i = 0; i < TH; ++i)
+      for (int j = 0; j < TW; ++j) {
+        const uint32_t nb = col_bits<TH>(nearm, r0, c0 + j);
 #pragma unroll
-        for (int j = 0; j < TW; ++j) {
+        for (int i = 0; i < TH; ++i) {
           const uint32_t hb = __float_as_uint(h[i + 1][j + 1]);
           if (hb < kInfBits) hmax = fmaxf(hmax, h[i + 1][j + 1]);
+          cf.cell(hb, (uint32_t)__builtin_amdgcn_sbfe(nb, i, 1));
         }
+      }
     }
     const bool exact = __syncthreads_or((hmax > kPinnedCost) || (it >= kMaxIters)) != 0;
     // ---- 3. raw cost out (occupied marker -> +inf) into the env's field tile: the field's 10 x 10 tiles are
     // these threads' tiles, so the 100 stores are immediate offsets of one base (no per-thread offsets, no
-    // scratch copy).  Statistics and the SDF in k_field_stats, the constants in k_field_norm ----
+    // scratch copy).  The near cells' statistics and the SDF in k_field_near, the constants in k_field_norm ----
     // (a TH x TW sweep tile is the column part (tc % kSub) of field tile (tr, tc / kSub))
     constexpr int kSub = USV_FIELD_TW / TW;
     static_assert(USV_FIELD_TCOLS * USV_FIELD_TW == G && USV_FIELD_TCOLS == NTC / kSub, "field tiles = sweep tiles");
@@ -444,17 +519,52 @@ __device__ __forceinline__ void field_wave_body(const usv_cfg_t &c, const usv_bu
       float *Fe = b.field + (size_t)e * FS;          // overwritten: the ping-pong buffer, then the cost tiles
       float *scratch = b.sdf + (size_t)e * FS;      // the other ping-pong buffer
       cost_sweeps_exact<NTHR>(occ, ix, iy, Fe, scratch);   // 225 (odd) sweeps: result in scratch
-      for (int q = tid; q < G2; q += NTHR) Fe[field_idx(q / G, q % G)] = scratch[q];
+      // the cost partial row again, from the costs this path stores (the registers hold the tile sweeps' costs);
+      // scratch[q] is this thread's own store of the last sweep
+      cf = CostFold{};
+      hmax = 0.f;
+      for (int q = tid; q < G2; q += NTHR) {
+        const float v = scratch[q];
+        const int r = q / G, cc = q % G;
+        Fe[field_idx(r, cc)] = v;
+        if (__float_as_uint(v) < kInfBits) hmax = fmaxf(hmax, v);
+        cf.cell(__float_as_uint(v), occ_bit(nearm, r, cc) ? 0xFFFFFFFFu : 0u);
+      }
       if (tid == 0) atomicAdd(&b.ctl[USV_CTL_FIELD_EXACT], 1);
     }
+    // ---- 4. the slot's cost partial row: per thread as the row's floats (min / max neutral where the thread
+    // has no such cell), folded over the wave, then over the waves in wave order by thread 0 ----
+    {
+      const bool fin = cf.gmin < kInfBits;
+      const float v0 = wave_min(fin ? __uint_as_float(cf.gmin) : INFINITY);   // finite-cost minimum
+      const float v1 = wave_max(fin ? hmax : -INFINITY);                      // finite-cost maximum
+      const float v2 = wave_max(cf.amax >= kInfBits ? 1.f : 0.f);             // some infinite cell
+      const float v3 = wave_min(cf.fmin < kInfBits ? 0.f : INFINITY);         // +0: some finite far cell
+      const float v4 = wave_min(cf.fmax >= kInfBits ? 0.f : INFINITY);        // +0: some infinite far cell
+      if (lane == 0) {
+        cred[0][wid] = v0; cred[1][wid] = v1; cred[2][wid] = v2; cred[3][wid] = v3; cred[4][wid] = v4;
+      }
+    }
+    __syncthreads();
     if (tid == 0) {
+      float a[5];
+      for (int k = 0; k < 5; ++k) a[k] = cred[k][0];
+      for (int v = 1; v < NTHR / 64; ++v) {
+        a[0] = fminf(a[0], cred[0][v]); a[1] = fmaxf(a[1], cred[1][v]); a[2] = fmaxf(a[2], cred[2][v]);
+        a[3] = fminf(a[3], cred[3][v]); a[4] = fminf(a[4], cred[4][v]);
+      }
+      // the far cells' J statistics are those of J = +0 at a cell that is not inside: where stat_far put them
+      float *pp = b.slot_stats + (size_t)slot * kSlotStride + kSlotCost;
+      pp[SS_GMIN_F] = a[0]; pp[SS_GMAX_F] = a[1]; pp[SS_ANY_INF] = a[2];
+      pp[SS_JMIN_F_NI] = a[3]; pp[SS_JMAX_F_NI] = a[3] == 0.f ? 0.f : -INFINITY; pp[SS_JMAX_F_ALL] = 0.f;
+      pp[SS_JRMIN_I_NI] = a[4]; pp[SS_JRMAX_I_NI] = a[4] == 0.f ? 0.f : -INFINITY; pp[SS_JRMAX_I_ALL] = 0.f;
+      pp[SS_INSIDE] = 0.f;
       b.slot_stats[(size_t)slot * kSlotStride + SS_ITERS] = (float)it;   // iterations (diagnostic)
       b.slot_stats[(size_t)slot * kSlotStride + SS_EXACT] = exact ? 1.f : 0.f;   // took the reference's sweeps
 #ifdef USV_PHASE_PROBE
       if (blockIdx.x < 4096) g_probe_field[blockIdx.x][15] = (unsigned long long)it;
 #endif
     }
-    __syncthreads();
     USV_PHASE(field, 3);
   }
 }
@@ -482,92 +592,41 @@ __device__ __forceinline__ BatchK batch_k(const usv_cfg_t &c, const usv_bufs_t &
 }
 
 // ------------------------------------------------------------- pass C1 ---
-// Per (slot, band of kBandRows grid rows): statistics split by finite / infinite cost so
-// the batch constant inf_val (known only when every env is done) enters
-// through one monotone scalar per batch.  Partials at slot_stats[slot][16 + 12 band].
-// The SDF is formed separably with cell_sdf's rounded operations: a thread owns two
-// adjacent columns, keeps (gx - ox)^2 of both for the obstacles in registers and,
-// per row, forms gy - oy once for the two cells -- fmaf(dy, dy, dx * dx), the same
-// min tree, sqrt, minus the radius: the same bits in about half the instructions.
-// Every statistic is a min / max (any grouping gives the same value), so the cells can be
-// dealt to threads in any shape: each wave owns a compact 38-column x 30-row block of the band
-// (19 column pairs x 3 row groups), so the obstacles that can reach it are few (a per-wave mask)
-// and many of its row strips lie out of every obstacle's reach, where the SDF cannot enter the
-// statistics and a cell contributes only through its cost (the "far" path below).
-// The obstacles a wave's block needs come from LDS through its mask, not from 48 registers held across the band:
-// with USV_STATS_WAVES 5 waves per SIMD instead of 4, -5% on the kernel late in training.
-// USV_STATS_WAVES: k_field_stats' minimum waves per SIMD (its register budget: 5 -> 96 VGPRs, no spills with the LDS
-// obstacles; 6 spills)
-#ifndef USV_STATS_WAVES
-#define USV_STATS_WAVES 5
-#endif
-constexpr int kBandRows = 30, kBands = G / kBandRows;       // row bands of a slot
-constexpr int kRowGroups = 3;                               // row groups per wave (rows rg, rg + 3, ...)
-constexpr int kWavePairs = 19;                              // column pairs per wave: 4 waves x 38 >= 150 columns
-constexpr int kBandIters = kBandRows / kRowGroups;          // rows per thread and band
-static_assert(G % kBandRows == 0 && kBandRows % kRowGroups == 0 && kWavePairs * kRowGroups <= 64 &&
-              4 * 2 * kWavePairs >= G && G % 2 == 0, "k_field_stats geometry");
-static_assert(kSlotObst >= 16 + 12 * kBands, "slot_stats band partials");
-__global__ __launch_bounds__(256, USV_STATS_WAVES) void k_field_stats(usv_cfg_t c, usv_bufs_t b) {
-  __shared__ float red[10][4];
-  __shared__ int flags[2];
+// Per slot: the J statistics and the inside flag of the cells inside the obstacles' windows (near_window), split
+// by finite / infinite cost so the batch constant inf_val (known only when every env is done) enters through one
+// monotone scalar per batch.  The partial row goes to slot_stats[slot][kSlotNear]; the cells outside every
+// window, and the cost statistics of all cells, are in the sweep kernel's row at kSlotCost.
+// Every statistic is a min / max (any grouping gives the same value, a cell counted twice changes nothing), so
+// the windows may overlap and need not be disjoint from what the sweep kernel called far: the two rows only have
+// to cover the grid between them.  They do: the sweep kernel's near map is the union of these same windows.
+// One workgroup per slot, wave v walks the windows of obstacles v, v + 4, ..: lane k takes window cells k, k + 64,
+// .. (row-major inside the window), gathers their costs from the env's tiles (all in flight at once), forms the
+// SDF with cell_sdf's rounded operations -- gx - ox, gy - oy, fmaf(dy, dy, dx * dx), u32 min, sqrt, minus the
+// radius -- over the obstacles that can reach the window (a far obstacle can only win the min where the SDF is
+// irrelevant: a per-window mask, uniform for the wave, the coordinates LDS broadcasts), and applies stat().
+constexpr int kNearWaves = 4;
+constexpr int kNearCells = 8;   // window cells per lane and round: 8 x 64 covers a 20 x 20 window in one round
+__global__ __launch_bounds__(64 * kNearWaves) void k_field_near(usv_cfg_t c, usv_bufs_t b) {
+  __shared__ float red[6][kNearWaves];
+  __shared__ int flag[kNearWaves];
   __shared__ float slin[G];
   __shared__ float so[2 * USV_NOBST];
   const int count = min(b.ctl[USV_CTL_RESET_COUNT], b.n);
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int cbase = wid * 2 * kWavePairs;                    // first column of this wave's block
-  const int cpl = lane % kWavePairs, rg = lane / kWavePairs;
-  const int c0u = cbase + 2 * cpl;
-  const bool act = rg < kRowGroups && c0u < G;               // other lanes only join the reductions
-  const int c0 = act ? c0u : 0;                              // (even: the pair is one tile row)
-  const int rgc = act ? rg : 0;
-  const int chi = min(cbase + 2 * kWavePairs - 1, G - 1);    // last column of the block
   const float cell = (float)((double)c.map_size / G);
+  const float half_m = (float)((double)c.map_size / 2);
   const float inv_r = (float)(1.0 / (double)c.influence_radius);
   const float inv_safe = 1.0f / c.safe_radius;   // goal_mask's quotient as div_rn (field_value's form)
-  // a cell whose squared distance to every obstacle in reach is >= far_d^2 has dte >= R + 1e-3 (jr = 0, not
-  // inside) whatever the rounding of the sqrt and the two subtractions: it enters only through its cost
-  const float far_d = c.influence_radius + 2.0f * c.obstacle_radius + 0.01f * cell + 1e-3f;
+  const float far_d = field_far_d(c, cell);
   const uint32_t far2 = __float_as_uint(far_d * far_d);
-  const int items = count * kBands;
   if (tid < G) slin[tid] = grid_coord(b.grid_lin, c.map_size, tid);
-  // the band's raw costs (two adjacent cells per row: one 8-byte load), all in flight at once
-  const auto load_costs = [&](int wq, int eq, float2 *dst) {
-    const float *F = b.field + (size_t)eq * FS;     // the raw cost tiles (k_field_wave / k_field_exact)
-#pragma unroll
-    for (int k = 0; k < kBandIters; ++k) {
-      const int r = (wq % kBands) * kBandRows + rgc + kRowGroups * k;
-      dst[k] = *reinterpret_cast<const float2 *>(F + field_idx(r, c0));
-    }
-  };
-  // one item: the statistics of band w % kBands of slot w / kBands, from the costs loaded into gv at its start
-  // (gv lives outside the item: as a local of it the kernel compiles to other code)
-  float2 gA[kBandIters];
-  const auto item = [&](const int w, float2 (&gv)[kBandIters]) {
-    const int slot = w / kBands, band = w % kBands;
+  for (int slot = blockIdx.x; slot < count; slot += gridDim.x) {
     if (tid < 2 * USV_NOBST) so[tid] = b.slot_stats[(size_t)slot * kSlotStride + kSlotObst + tid];
-    if (tid < 2) flags[tid] = 0;
+    const float *F = b.field + (size_t)b.reset_ids[slot] * FS;   // the raw cost tiles (k_field_wave*)
     __syncthreads();
-    load_costs(w, b.reset_ids[slot], gv);
-    const float gxa = slin[c0], gxb = slin[c0 + 1];
-    // Obstacles that can matter to this wave's block: the SDF enters the statistics only through j_raw (0
-    // unless dist - 2 r_obs < influence_radius) and the inside test (dist <= 2 r_obs), so an obstacle farther
-    // than far_d from the whole block (in x or in y) can only be the minimum of a cell whose SDF is irrelevant
-    // (jr = 0, not inside, with the exact SDF and with the smaller set alike).  Uniform per wave.
-    uint32_t omask;
-    {
-      const float ylo = slin[band * kBandRows], yhi = slin[band * kBandRows + kBandRows - 1];
-      const float xlo = slin[cbase], xhi = slin[chi];
-      const int ol = lane & (USV_NOBST - 1);
-      const float oxl = so[2 * ol], oyl = so[2 * ol + 1];
-      const float dyb = fmaxf(fmaxf(ylo - oyl, oyl - yhi), 0.f);
-      const float dxb_ = fmaxf(fmaxf(xlo - oxl, oxl - xhi), 0.f);
-      omask = (uint32_t)(__ballot(lane < USV_NOBST && !(dyb > far_d) && !(dxb_ > far_d)) & 0xFFFFull);
-      omask = __builtin_amdgcn_readfirstlane(omask);
-    }
-    float gmin = INFINITY, gmax = -INFINITY, jmin_f = INFINITY, jmax_f = -INFINITY, jall_f = 0.f;
+    float jmin_f = INFINITY, jmax_f = -INFINITY, jall_f = 0.f;
     float jrmin_i = INFINITY, jrmax_i = -INFINITY, jrall_i = 0.f;
-    int any_inf = 0, inside = 0;
+    int inside = 0;
     // branch-free: each statistic takes its cell's value or the neutral element of its min / max
     const auto stat = [&](float g, float sv) {
       const float dte = sv - c.obstacle_radius;
@@ -575,15 +634,12 @@ __global__ __launch_bounds__(256, USV_STATS_WAVES) void k_field_stats(usv_cfg_t 
       inside |= ins;
       const float jr = j_raw(c, dte, inv_r);
       const bool gi = isinf(g);
-      any_inf |= gi;
       // goal_mask(c, g, cell) as div_rn by the correctly rounded reciprocal: the same bits for every finite
       // g (usv_device.h div_rn); an infinite g gives NaN here, and j is only read where g is finite
       const float j = jr * clampt(div_rn(g * cell, c.safe_radius, inv_safe), 0.f, 1.f);
       jrall_i = fmaxf(jrall_i, gi ? jr : 0.f);
       jrmin_i = fminf(jrmin_i, (gi && !ins) ? jr : INFINITY);
       jrmax_i = fmaxf(jrmax_i, (gi && !ins) ? jr : -INFINITY);
-      gmin = fminf(gmin, gi ? INFINITY : g);
-      gmax = fmaxf(gmax, gi ? -INFINITY : g);
       jall_f = fmaxf(jall_f, gi ? 0.f : j);
       jmin_f = fminf(jmin_f, (!gi && !ins) ? j : INFINITY);
       jmax_f = fmaxf(jmax_f, (!gi && !ins) ? j : -INFINITY);
@@ -592,87 +648,103 @@ __global__ __launch_bounds__(256, USV_STATS_WAVES) void k_field_stats(usv_cfg_t 
     // there, without the sqrt and the divisions (jall_f and jrall_i take max(., +0), a no-op from their +0 start)
     const auto stat_far = [&](float g) {
       const bool gi = isinf(g);
-      any_inf |= gi;
       jrmin_i = fminf(jrmin_i, gi ? 0.f : INFINITY);
       jrmax_i = fmaxf(jrmax_i, gi ? 0.f : -INFINITY);
-      gmin = fminf(gmin, gi ? INFINITY : g);
-      gmax = fmaxf(gmax, gi ? -INFINITY : g);
       jmin_f = fminf(jmin_f, gi ? INFINITY : 0.f);
       jmax_f = fmaxf(jmax_f, gi ? -INFINITY : 0.f);
     };
-    // squared distances (non-negative: u32 min of the bit patterns is the float min, exact in any
-    // order), obstacle-outer so a skipped obstacle is one scalar branch for the block's rows
-    float gy[kBandIters];
-    uint32_t a[kBandIters], bb[kBandIters];
-#pragma unroll
-    for (int k = 0; k < kBandIters; ++k) {
-      gy[k] = slin[band * kBandRows + rgc + kRowGroups * k];
-      a[k] = bb[k] = 0x7F800000u;
-    }
-    // the mask's obstacles only (a scalar loop over its set bits; the coordinates are LDS broadcasts): no
-    // per-obstacle registers
-    for (uint32_t om = omask; om != 0u; om &= om - 1u) {
-      const int o = __builtin_ctz(om);
-      const float ox = so[2 * o], oyo = so[2 * o + 1];
-      const float da = gxa - ox, db = gxb - ox;
-      const float dxa = da * da, dxb = db * db;
-#pragma unroll
-      for (int k = 0; k < kBandIters; ++k) {
-        const float dy = gy[k] - oyo;
-        a[k] = min(a[k], __float_as_uint(fmaf(dy, dy, dxa)));
-        bb[k] = min(bb[k], __float_as_uint(fmaf(dy, dy, dxb)));
+    for (int o = wid; o < USV_NOBST; o += kNearWaves) {   // (uniform per wave)
+      const Win w = near_window(so[2 * o], so[2 * o + 1], half_m, cell, far_d);
+      if (w.cl > w.ch) continue;
+      const int ww = w.ch - w.cl + 1, area = ww * (w.rh - w.rl + 1);
+      const float inv_ww = 1.0f / (float)ww;
+      // Obstacles that can matter to this window: one farther than far_d from the whole window (in x or in y)
+      // can only be the minimum of a cell whose SDF is irrelevant (jr = 0, not inside, with the exact SDF and
+      // with the smaller set alike).  Obstacle o itself is always in the set.
+      uint32_t omask;
+      {
+        const float ylo = slin[w.rl], yhi = slin[w.rh], xlo = slin[w.cl], xhi = slin[w.ch];
+        const int ol = lane & (USV_NOBST - 1);
+        const float oxl = so[2 * ol], oyl = so[2 * ol + 1];
+        const float dyb = fmaxf(fmaxf(ylo - oyl, oyl - yhi), 0.f);
+        const float dxb = fmaxf(fmaxf(xlo - oxl, oxl - xhi), 0.f);
+        omask = (uint32_t)(__ballot(lane < USV_NOBST && !(dyb > far_d) && !(dxb > far_d)) & 0xFFFFull);
+        omask = __builtin_amdgcn_readfirstlane(omask);
       }
-    }
+      for (int k0 = 0; k0 < area; k0 += 64 * kNearCells) {
+        float g[kNearCells], gx[kNearCells], gy[kNearCells];
+        uint32_t a[kNearCells];
+        bool ok[kNearCells];
 #pragma unroll
-    for (int k = 0; k < kBandIters; ++k) {
-      // a row strip of the block whose cells all lie out of reach takes the far path (uniform branch)
-      const bool near = act && (a[k] < far2 || bb[k] < far2);
-      if (__ballot(near) != 0ull) {
-        const float sva = sqrtf(__uint_as_float(a[k])) - c.obstacle_radius;
-        const float svb = sqrtf(__uint_as_float(bb[k])) - c.obstacle_radius;
-        if (act) {
-          stat(gv[k].x, sva);
-          stat(gv[k].y, svb);
+        for (int u = 0; u < kNearCells; ++u) {
+          const int k = k0 + 64 * u + lane;
+          ok[u] = k < area;
+          // k / ww for k < 2^20 and ww <= 150: (k + 0.5) / ww is at least 1 / 300 away from an integer
+          const int kr = ok[u] ? (int)(((float)k + 0.5f) * inv_ww) : 0;
+          const int r = w.rl + kr, cc = w.cl + (ok[u] ? k - kr * ww : 0);
+          g[u] = F[field_idx(r, cc)];
+          gx[u] = slin[cc];
+          gy[u] = slin[r];
+          a[u] = 0x7F800000u;
         }
-      } else if (act) {
-        stat_far(gv[k].x);
-        stat_far(gv[k].y);
+        // squared distances (non-negative: u32 min of the bit patterns is the float min, exact in any order)
+        for (uint32_t om = omask; om != 0u; om &= om - 1u) {
+          const int p = __builtin_ctz(om);
+          const float ox = so[2 * p], oy = so[2 * p + 1];
+#pragma unroll
+          for (int u = 0; u < kNearCells; ++u) {
+            const float dx = gx[u] - ox, dy = gy[u] - oy;
+            a[u] = min(a[u], __float_as_uint(fmaf(dy, dy, dx * dx)));
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < kNearCells; ++u) {
+          // a round of cells that all lie out of reach takes the far path (uniform branch)
+          const bool near = ok[u] && a[u] < far2;
+          if (__ballot(near) != 0ull) {
+            const float sv = sqrtf(__uint_as_float(a[u])) - c.obstacle_radius;
+            if (ok[u]) stat(g[u], sv);
+          } else if (ok[u]) {
+            stat_far(g[u]);
+          }
+        }
       }
     }
-    float vals[9] = {wave_min(gmin), wave_max(gmax), wave_min(jmin_f), wave_max(jmax_f), wave_max(jall_f),
-                     wave_min(jrmin_i), wave_max(jrmax_i), wave_max(jrall_i), 0.f};
-    __syncthreads();   // flags reset visible
-    if (lane == 0)
-      for (int k = 0; k < 8; ++k) red[k][wid] = vals[k];
-    if (any_inf) flags[0] = 1;
-    if (inside) flags[1] = 1;
+    // (every lane is here: the window loop's branches are uniform per wave)
+    const float v0 = wave_min(jmin_f), v1 = wave_max(jmax_f), v2 = wave_max(jall_f);
+    const float v3 = wave_min(jrmin_i), v4 = wave_max(jrmax_i), v5 = wave_max(jrall_i);
+    const bool ins_w = __ballot(inside != 0) != 0ull;
+    if (lane == 0) {
+      red[0][wid] = v0; red[1][wid] = v1; red[2][wid] = v2; red[3][wid] = v3; red[4][wid] = v4; red[5][wid] = v5;
+      flag[wid] = ins_w;
+    }
     __syncthreads();
     if (tid == 0) {
-      float a[8];
-      for (int k = 0; k < 8; ++k) a[k] = red[k][0];
-      for (int v = 1; v < 4; ++v) {
-        a[0] = fminf(a[0], red[0][v]); a[1] = fmaxf(a[1], red[1][v]);
-        a[2] = fminf(a[2], red[2][v]); a[3] = fmaxf(a[3], red[3][v]); a[4] = fmaxf(a[4], red[4][v]);
-        a[5] = fminf(a[5], red[5][v]); a[6] = fmaxf(a[6], red[6][v]); a[7] = fmaxf(a[7], red[7][v]);
+      float r[6];
+      int in = flag[0];
+      for (int k = 0; k < 6; ++k) r[k] = red[k][0];
+      for (int v = 1; v < kNearWaves; ++v) {
+        r[0] = fminf(r[0], red[0][v]); r[1] = fmaxf(r[1], red[1][v]); r[2] = fmaxf(r[2], red[2][v]);
+        r[3] = fminf(r[3], red[3][v]); r[4] = fmaxf(r[4], red[4][v]); r[5] = fmaxf(r[5], red[5][v]);
+        in |= flag[v];
       }
-      float *pp = b.slot_stats + (size_t)slot * kSlotStride + 16 + 12 * band;
-      pp[SS_GMIN_F] = a[0]; pp[SS_GMAX_F] = a[1]; pp[SS_ANY_INF] = flags[0] ? 1.f : 0.f;
-      pp[SS_JMIN_F_NI] = a[2]; pp[SS_JMAX_F_NI] = a[3]; pp[SS_JMAX_F_ALL] = a[4];
-      pp[SS_JRMIN_I_NI] = a[5]; pp[SS_JRMAX_I_NI] = a[6]; pp[SS_JRMAX_I_ALL] = a[7];
-      pp[SS_INSIDE] = flags[1] ? 1.f : 0.f;
-      // the batch max of finite costs (:205-210) is folded from these band maxima by
-      // k_field_batch (one atomic per band on a single address serialised this kernel)
+      // (the cost statistics of every cell, near ones included, are the sweep kernel's: neutral here)
+      float *pp = b.slot_stats + (size_t)slot * kSlotStride + kSlotNear;
+      pp[SS_GMIN_F] = INFINITY; pp[SS_GMAX_F] = -INFINITY; pp[SS_ANY_INF] = 0.f;
+      pp[SS_JMIN_F_NI] = r[0]; pp[SS_JMAX_F_NI] = r[1]; pp[SS_JMAX_F_ALL] = r[2];
+      pp[SS_JRMIN_I_NI] = r[3]; pp[SS_JRMAX_I_NI] = r[4]; pp[SS_JRMAX_I_ALL] = r[5];
+      pp[SS_INSIDE] = in ? 1.f : 0.f;
     }
-    __syncthreads();
-  };
-  for (int w = blockIdx.x; w < items; w += gridDim.x) item(w, gA);
+    // (the next slot's so[] stores follow this barrier; thread 0 has read red[] before the next slot's first one)
+  }
 }
 
 // ------------------------------------------------------------- pass C2 ---
-// fold each slot's chunk partials (chunk order), then the batch maxima: the max of
-// finite costs (d_multi_gemini.py:205-210), J.max() (:257-260) and the any-inside
-// flag.  Six slots per wave (lane 10 g + q folds statistic q of the wave's slot g over the chunks: one cache
-// line per chunk row instead of a scattered load per statistic and slot), waves of
+// fold each slot's two partial rows (the sweep kernel's cost row, whose far-cell entries are +0 or the neutral
+// element -- min(., +0) / max(., +0) where stat_far applied them -- then k_field_near's), then the batch maxima:
+// the max of finite costs (d_multi_gemini.py:205-210), J.max() (:257-260) and the any-inside
+// flag.  Six slots per wave (lane 10 g + q folds statistic q of the wave's slot g over the rows: one cache
+// line per slot instead of a scattered load per statistic and slot), waves of
 // kBatchBlocks workgroups loop over the slots; the batch maxima leave through max
 // atomics (exact in any order, one set per workgroup) and the last workgroup forms
 // J.max() = max(J over finite cells, mask(inf_val) * raw J over infinite cells) --
@@ -680,7 +752,7 @@ __global__ __launch_bounds__(256, USV_STATS_WAVES) void k_field_stats(usv_cfg_t 
 // products is the product with the max.
 // USV_BATCH_BLOCKS: the batch fold's workgroups (64; 256 measured slower: the per-workgroup max atomics
 // contend).  USV_BATCH_SLOTS_PER_WAVE: slots per wave and round (6: lanes 0-59; 1: lanes 0-9, one dependent round of
-// band-partial loads per slot, ~8 rounds at ~2,000 resets per step)
+// partial-row loads per slot, ~8 rounds at ~2,000 resets per step)
 #ifndef USV_BATCH_BLOCKS
 #define USV_BATCH_BLOCKS 64
 #endif
@@ -707,12 +779,12 @@ __global__ __launch_bounds__(256) void k_field_batch(usv_cfg_t c, usv_bufs_t b) 
     float a = 0.f;
     if (ok) {
       float *st = b.slot_stats + (size_t)sl * kSlotStride;
-      float x[kBands];
+      float x[kParts];
 #pragma unroll
-      for (int ch = 0; ch < kBands; ++ch) x[ch] = st[16 + 12 * ch + q];
+      for (int ch = 0; ch < kParts; ++ch) x[ch] = st[kSlotCost + 12 * ch + q];
       a = x[0];
 #pragma unroll
-      for (int ch = 1; ch < kBands; ++ch) a = is_min ? fminf(a, x[ch]) : fmaxf(a, x[ch]);
+      for (int ch = 1; ch < kParts; ++ch) a = is_min ? fminf(a, x[ch]) : fmaxf(a, x[ch]);
       st[q] = a;
     }
     // the slot's folded statistics from its group's lanes (lanes without a slot read themselves, unused)
@@ -811,12 +883,12 @@ __global__ __launch_bounds__(256) void k_field_view(usv_cfg_t c, usv_bufs_t b, c
 }  // namespace
 
 namespace {
-// stage 1: the obstacle placement alone (k_field_place); stage 2: the rest after it (sweeps, exactness
-// fallback, statistics, batch fold, constants) = stage 3 (sweeps, fallback, statistics) + stage 4 (batch fold,
-// constants)
-// k_field_stats' grid: workgroups loop over (slot, band) items, at most kStatsGridCap of them
-constexpr int kStatsGridCap = 4096;
-static int stats_grid(int n) { return n * kBands < kStatsGridCap ? n * kBands : kStatsGridCap; }
+// stage 1: the obstacle placement alone (k_field_place); stage 2: the rest after it (sweeps with the exactness
+// fallback and the cost statistics, near-cell statistics, batch fold, constants) = stage 3 (sweeps, near-cell
+// statistics) + stage 4 (batch fold, constants)
+// k_field_near's grid: workgroups loop over the slots, at most kNearGridCap of them (256 CUs x 8 resident)
+constexpr int kNearGridCap = 2048;
+static int near_grid(int n) { return n < kNearGridCap ? n : kNearGridCap; }
 
 int field_stages(const usv_cfg_t *cfg, const usv_bufs_t *b, int stage, hipStream_t s) {
   const int grid_b = b->n < 512 ? b->n : 512;
@@ -838,8 +910,7 @@ int field_stages(const usv_cfg_t *cfg, const usv_bufs_t *b, int stage, hipStream
       hipLaunchKernelGGL(k_field_wave_pack, dim3(grid_w), dim3(kWaveThreads), 0, s, *cfg, *b);
     }
     USV_CHECK_LAUNCH();
-    const int grid_s = stats_grid(b->n);
-    hipLaunchKernelGGL(k_field_stats, dim3(grid_s), dim3(256), 0, s, *cfg, *b);
+    hipLaunchKernelGGL(k_field_near, dim3(near_grid(b->n)), dim3(64 * kNearWaves), 0, s, *cfg, *b);
     USV_CHECK_LAUNCH();
   }
   if (stage == 2 || stage == 4) {
@@ -889,8 +960,7 @@ extern "C" int usv_potential_field(const usv_cfg_t *cfg, const usv_bufs_t *b, vo
                               *cfg, *b);
   else hipLaunchKernelGGL(k_field_wave, dim3(grid_b), dim3(kWaveThreads), 0, s, *cfg, *b);
   USV_CHECK_LAUNCH();
-  const int grid_s = stats_grid(b->n);
-  hipLaunchKernelGGL(k_field_stats, dim3(grid_s), dim3(256), 0, s, *cfg, *b);
+  hipLaunchKernelGGL(k_field_near, dim3(near_grid(b->n)), dim3(64 * kNearWaves), 0, s, *cfg, *b);
   USV_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_field_batch, dim3(kBatchBlocks), dim3(256), 0, s, *cfg, *b);
   USV_CHECK_LAUNCH();
