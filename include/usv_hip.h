@@ -690,6 +690,57 @@ int usv_teval_step(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_teval_t 
 int usv_teval_summary(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_teval_t *tev, double *out, void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* Policy banks: M checkpoints evaluated in one rollout of n = M x G envs    */
+/* (scripts/multi_model_eval.py: eval_multi_agents :39-113), envs            */
+/* [m G, (m + 1) G) under model m (ppo_policy_bank_step)                     */
+/* ------------------------------------------------------------------------ */
+/* rows of usv_bank_t.motion ([USV_BEV_ROWS][n] doubles, updated in place) */
+#define USV_BEV_SPEED_SUM    0   /* double sum of the float32 norm(obs[0], obs[1]) over the horizon */
+#define USV_BEV_YAWRATE_SUM  1   /* double sum of |obs[2]| */
+#define USV_BEV_ACT_SUM      2   /* double sum of act[0] + act[1] (the actions handed to the env step) */
+#define USV_BEV_STEPS        3   /* usv_bank_step calls since usv_bank_begin, the ones past horizon included */
+#define USV_BEV_ROWS         4
+/* a row of usv_bank_summary's output ([models][USV_BEVS_N] doubles): usv_teval_summary's [USV_TEVS_N] of the
+ * group alone, then */
+#define USV_BEVS_SPEED_SUM   23   /* group totals of the three motion sums */
+#define USV_BEVS_YAWRATE_SUM 24
+#define USV_BEVS_ACT_SUM     25
+#define USV_BEVS_PAIRS       26   /* (step, env) pairs in those sums: the group's total of min(STEPS, horizon) */
+#define USV_BEVS_N           27
+
+typedef struct usv_bank {
+  double *motion;   /* [USV_BEV_ROWS][n] */
+  int     models;   /* M */
+  int     group;    /* G: n = M x G */
+  int     horizon;  /* evaluated steps (usv_teval_t.horizon) */
+} usv_bank_t;
+
+/* The paired run's random words: env e of the bank gets the words env e % group of a group-env run would draw.
+ * u_step [n][USV_NU_STEP]: every row, Philox(seed, e % group, step, site 0 / 1) in the SU_* layout (words 4..7 zero
+ * when neither position nor action noise is on, as the step kernel leaves them).  u_reset [n][USV_NU_RESET]: the
+ * rows of the envs with reset_buf != 0 (the only rows usv_reset reads), slot i = word i & 3 of site 0x100 + (i >> 2);
+ * the other rows are left alone.  To be called before the usv_reset / usv_env_step pair it feeds, with the step index
+ * that pair is about to use; where the env buffers carry the device step clock (usv_bufs_t.clock) its next index is
+ * used instead of `step`, as the kernels do.  Status 1: a NULL argument or buffer (reset_buf), n <= 0; status 2:
+ * group < 1 or n % group != 0. */
+int usv_bank_uniforms(const usv_cfg_t *cfg, const usv_bufs_t *b, int group, uint64_t seed, uint64_t step,
+                      float *u_step, float *u_reset, void *stream);
+/* Status 1: a NULL argument, motion table, env buffer (obs), actions or output, n <= 0; status 2: models < 1,
+ * group < 1, n != models * group or horizon < 1 (any group size: the multiple of 32 is ppo_policy_bank_step's).
+ * All checks precede device work.  No atomics.  usv_bank_begin zeroes the motion table. */
+int usv_bank_begin(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_bank_t *bank, void *stream);
+/* after usv_teval_step, with the actions [n][2] the env step consumed.  The norm is formed as usv_teval_step forms
+ * its own (float32 products and sum without contraction, sqrtf); each term is added in double.  A step past horizon
+ * is counted in STEPS and otherwise ignored. */
+int usv_bank_step(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_bank_t *bank, const float *actions,
+                  void *stream);
+/* out [models][USV_BEVS_N] (device), one workgroup per group.  The first USV_TEVS_N entries of row m are the bits
+ * usv_teval_summary writes for a table holding group m's envs alone (the same fold order from the group's first
+ * env; tev's statuses apply).  The same tables give the same bits. */
+int usv_bank_summary(const usv_cfg_t *cfg, const usv_bufs_t *b, const usv_teval_t *tev, const usv_bank_t *bank,
+                     double *out, void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Scenario tables (scripts/build_usv_scenario_table.py: sampling :153-209,  */
 /* metrics :215-258; scripts/teacher_filter_scenario_table.py: the           */
 /* per-scenario aggregate :712-759 and the filter's verdict :512-552)        */
@@ -921,6 +972,17 @@ int ppo_policy_step(const ppo_cfg_t *cfg, const float *params, const double *obs
                     const int64_t *dones_prev, float *actions_out,
                     uint64_t seed, uint64_t step, const uint64_t *step_dev,
                     const float *eps_inject, void *stream);
+
+/* The deterministic policy step of a bank of checkpoints in one launch: actions_out [n][2] row e =
+ * clamp(mu, -1, 1) of obs row e under model e / group -- bank_params [models][PPO_NPARAM], bank_obs_rms
+ * [models][2 * PPO_NIN + 1] doubles (mean, var, count per model); the bits of ppo_policy_step's mu with that model
+ * alone on those rows.  No sampling, no experience stores, no value.  Of cfg: n_envs, normalize_input, rms_eps,
+ * nan_probe / nan_flag (as ppo_policy_step).  grid_cap: 0 = the default grid, else at most that many workgroups
+ * (the results do not depend on it).  Status 1: a NULL pointer; status 2: models < 1, group < 32, group % 32 != 0
+ * (a 32-row tile has one model) or n_envs != models * group.  All checks precede device work. */
+int ppo_policy_bank_step(const ppo_cfg_t *cfg, const float *bank_params, const double *bank_obs_rms,
+                         const float *obs, int models, int group, float *actions_out, int grid_cap,
+                         void *stream);
 
 /* Value of the last observation (A2CBase.get_values, a2c_common.py:407-430). */
 int ppo_value(const ppo_cfg_t *cfg, const float *params, const double *obs_rms,

@@ -96,6 +96,10 @@ class UsvTEval(ctypes.Structure):
     _fields_ = _struct_fields(_TXT, "usv_teval", DEFINES)
 
 
+class UsvBank(ctypes.Structure):
+    _fields_ = _struct_fields(_TXT, "usv_bank", DEFINES)
+
+
 class LzCfg(ctypes.Structure):
     _fields_ = _struct_fields(_TXT, "lz_cfg", DEFINES)
 
@@ -139,12 +143,12 @@ PEN = enum_values("usv_pen_kind")
 # usv_hip_layout_key(); _capi.lib() refuses a library whose key differs from layout_key() here, so a
 # library built from another header -- a moved slab row, a resized buffer, a reordered struct --
 # fails loudly before its first call instead of addressing past a buffer.
-LAYOUT_STRUCTS = ("usv_cfg", "usv_bufs", "usv_hydro", "usv_eval", "usv_teval", "ppo_cfg", "ppo_adam_banks", "ppo_dp",
-                  "lz_cfg")
+LAYOUT_STRUCTS = ("usv_cfg", "usv_bufs", "usv_hydro", "usv_eval", "usv_teval", "usv_bank", "ppo_cfg", "ppo_adam_banks",
+                  "ppo_dp", "lz_cfg")
 LAYOUT_ENUMS = ("usv_stat_key", "usv_pen_kind", "usv_dist_row")
 _STRUCT_CLASSES = {"usv_cfg": UsvCfg, "usv_bufs": UsvBufs, "usv_hydro": UsvHydro, "usv_eval": UsvEval,
-                   "usv_teval": UsvTEval, "ppo_cfg": PpoCfg, "ppo_adam_banks": PpoAdamBanks, "ppo_dp": PpoDp,
-                   "lz_cfg": LzCfg}
+                   "usv_teval": UsvTEval, "usv_bank": UsvBank, "ppo_cfg": PpoCfg, "ppo_adam_banks": PpoAdamBanks,
+                   "ppo_dp": PpoDp, "lz_cfg": LzCfg}
 GUARD_DEFINES = ("USV_HIP_H",)
 
 

@@ -13,7 +13,7 @@ import subprocess
 
 import torch  # noqa: F401  -- load torch's HIP runtime first; the .so binds to it (same SONAME)
 
-from ._abi import PpoCfg, UsvBufs, UsvCfg, UsvEval, UsvTEval
+from ._abi import PpoCfg, UsvBank, UsvBufs, UsvCfg, UsvEval, UsvTEval
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -22,9 +22,10 @@ LIB_PATH = os.path.join(LIB_DIR, "libusv_hip.so")
 # instrumented build (per-workgroup phase timestamps, tools/phase_probe.py); selected with USV_HIP_PROBE=1
 PROBE_LIB_PATH = os.path.join(LIB_DIR, "libusv_hip_probe.so")
 SOURCES = [os.path.join(HERE, "csrc", f) for f in ("usv_env.hip", "usv_field.hip", "usv_eval.hip", "usv_task_eval.hip",
-                                                    "ppo.hip", "loopz.hip", "usv_sysid.hip", "usv_scenario.hip",
+                                                    "usv_bank.hip", "ppo.hip", "loopz.hip", "usv_sysid.hip", "usv_scenario.hip",
                                                     "usv_compare.hip", "usv_analysis.hip")]
-DEPS = SOURCES + [os.path.join(HERE, "csrc", "usv_device.h"), os.path.join(HERE, "csrc", "usv_layout_gen.h"),
+DEPS = SOURCES + [os.path.join(HERE, "csrc", "usv_device.h"), os.path.join(HERE, "csrc", "usv_tev_fold.h"),
+                  os.path.join(HERE, "csrc", "usv_layout_gen.h"),
                   os.path.join(ROOT, "include", "usv_hip.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17",
@@ -74,6 +75,10 @@ def _declare(lib):
         "usv_teval_begin": [P, P, P, P],
         "usv_teval_step": [P, P, P, P],
         "usv_teval_summary": [P, P, P, P, P],
+        "usv_bank_uniforms": [P, P, I, U64, U64, P, P, P],
+        "usv_bank_begin": [P, P, P, P],
+        "usv_bank_step": [P, P, P, P, P],
+        "usv_bank_summary": [P, P, P, P, P, P],
         "usv_scn_generate": [U64, I64, I, D, D, D, D, D, I, I, P, P, P],
         "usv_scn_metrics": [P, I, D, D, P, P],
         "usv_scn_fold": [P, I, I, I, I, D, I, D, I, P, P],
@@ -91,6 +96,7 @@ def _declare(lib):
         "lz_minibatch_rows": [P, P, P, P, P, I, I, P, P, P, P, P, P, P, P, P, P],
         "lz_enforce_min_std": [P, P, P],
         "ppo_policy_step": [P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, U64, U64, P, P, P],
+        "ppo_policy_bank_step": [P, P, P, P, I, I, P, I, P],
         "ppo_value": [P, P, P, P, P, P, P],
         "ppo_store_reward": [P, P, P, I, P, P, P, P, P, P, P],
         "ppo_prepare": [P, P, P, P, P, P, P, P, P, P, P, P, P],
@@ -188,4 +194,4 @@ def byref(s):
 
 
 __all__ = ["build", "lib", "call", "call_rc", "ptr", "stream_ptr", "byref", "UsvCfg", "UsvBufs", "UsvEval", "UsvTEval",
-           "PpoCfg", "LIB_PATH"]
+           "UsvBank", "PpoCfg", "LIB_PATH"]

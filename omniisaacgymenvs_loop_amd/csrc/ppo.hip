@@ -222,7 +222,8 @@ __device__ __forceinline__ void load_obs_tile3(const float *__restrict__ obs, in
     x[u] = obs[(size_t)(row0 + r) * NIN + kc];
   }
 }
-template <class S>
+// kExp = false: no experience store (exp_obs is not read; k_policy_bank)
+template <class S, bool kExp = true>
 __device__ __forceinline__ void put_obs_tile3(const float (&x)[NUO3], int tt, int row0, int nrows, bool normalize,
                                               float eps, S &s, float *exp_obs, int H, int t) {
 #pragma unroll
@@ -233,7 +234,7 @@ __device__ __forceinline__ void put_obs_tile3(const float (&x)[NUO3], int tt, in
     float v = 0.f;
     if (r < nrows && k < NIN) {
       v = x[u];
-      exp_st(&exp_obs[((size_t)(row0 + r) * H + t) * NIN + k], v);
+      if constexpr (kExp) exp_st(&exp_obs[((size_t)(row0 + r) * H + t) * NIN + k], v);
       if (normalize) v = clampt((v - s.om[k]) / s.od[k], -5.0f, 5.0f);   // = rms_norm
     }
     s.x[q] = v;
@@ -552,6 +553,66 @@ __global__ __launch_bounds__(TB, kRW ? POL_WPC : 1) void k_policy_step(ppo_cfg_t
   if (threadIdx.x == 0 && blockIdx.x < 4096)
     for (int k = 0; k < 5; ++k) g_probe_pol[blockIdx.x][5 + k] = pa.d[k];
 #endif
+}
+
+// The deterministic policy step of a bank of `models` weight sets (bank_P [models][PPO_NPARAM], bank_rms
+// [models][2 NIN + 1]): rows [m * group, (m + 1) * group) run under model m and get clamp(mu, -1, 1); no sampling,
+// no experience stores, no value de-normalisation.  group is a multiple of RB, so a tile has one model.  The same
+// regw_load / obs staging / block_forward_rw as k_policy_step<true>: the same bits as that kernel's mu with model
+// m alone on those rows.  Persistent: workgroup b owns the contiguous tiles [b ntiles / grid, (b + 1) ntiles /
+// grid), so it changes model (RegW, the LDS tail, om / od) once or twice; every tile is computed from its own
+// model and rows only, so the results do not depend on the grid.  Per tile, waves 1-3 stage the rows (loaded
+// during the previous forward) while wave 0 writes the previous tile's actions; one barrier outside the forward,
+// one more at a model change (om / od are written by wave 0 and read by the staging waves).
+__global__ __launch_bounds__(TB, POL_WPC) void k_policy_bank(ppo_cfg_t c, const float *__restrict__ bank_P,
+                                                             const double *__restrict__ bank_rms,
+                                                             const float *__restrict__ obs, int group,
+                                                             float *__restrict__ actions_out) {
+  __shared__ PolSmem s;
+  const int n = c.n_envs;
+  const int ntiles = n / RB, tpm = group / RB;   // (n = models * group, group % RB == 0: checked by the host)
+  const int t0 = (int)((long long)blockIdx.x * ntiles / (int)gridDim.x);
+  const int t1 = (int)((long long)(blockIdx.x + 1) * ntiles / (int)gridDim.x);
+  if (t0 >= t1) return;   // (the grid is at most ntiles; uniform)
+  const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int tt = (int)threadIdx.x - 64;
+  const bool normalize = c.normalize_input != 0;
+  RegW wr;
+  PolAcc pa{};
+  int model = -1;
+  float xo[NUO3];
+  if (w > 0) load_obs_tile3(obs, n, t0, tt, xo);
+  for (int tile = t0; tile < t1; ++tile) {
+    const int m = tile / tpm;
+    if (m != model) {   // uniform.  s.tail was last read by the previous forward's heads, s.om / s.od by the
+      model = m;        // previous staging: both before that forward's closing barrier
+      regw_load(bank_P + (size_t)m * PPO_NPARAM, wr);
+      const double *rms = bank_rms + (size_t)m * (2 * NIN + 1);
+      if (threadIdx.x < NIN) {
+        s.om[threadIdx.x] = (float)rms[threadIdx.x];
+        s.od[threadIdx.x] = sqrtf((float)rms[NIN + threadIdx.x] + c.rms_eps);
+      }
+      regw_store_tail(wr, s);
+      __syncthreads();
+    }
+    // the slot indices recomputed per tile, opaque to the optimiser (as k_policy_step: hoisted they hold ~50 VGPRs)
+    int ttv = tt;
+    __asm__ volatile("" : "+v"(ttv));
+    // s.x was last read by the previous forward's layer 1 (before its first barrier)
+    if (w > 0) put_obs_tile3<PolSmem, false>(xo, ttv, tile * RB, RB, normalize, c.rms_eps, s, nullptr, 1, 0);
+    __syncthreads();
+    if (w > 0 && tile + 1 < t1) load_obs_tile3(obs, n, tile + 1, ttv, xo);   // in flight during the forward
+    block_forward_rw(wr, s, pa);
+    if (w == 0) {   // lane 32 j + r: row r's action component j.  s.out is rewritten by the next forward's heads,
+      const int r = lane & (RB - 1), j = lane >> 5;   // two barriers from here
+      actions_out[2 * (size_t)(tile * RB + r) + j] = clampt(s.out[r * 4 + j], -1.0f, 1.0f);
+      if (c.nan_probe && c.nan_flag) {   // wave 0, uniform
+        const bool bad = lane < RB && (nonfinite(s.out[lane * 4]) | nonfinite(s.out[lane * 4 + 1]) |
+                                       nonfinite(s.out[lane * 4 + 2]));
+        nan_report(c.nan_flag, bad ? USV_NAN_POLICY : 0u);
+      }
+    }
+  }
 }
 
 // kRW: the register-weight form of the policy step (RegW / PolSmem), up to 256 x POL_WPC workgroups
@@ -2286,6 +2347,19 @@ int ppo_policy_step(const ppo_cfg_t *cfg, const float *params, const double *obs
   hipLaunchKernelGGL(reg_w ? k_policy_step<true> : k_policy_step<false>, dim3(grid), dim3(TB), 0, (hipStream_t)stream,
                      *cfg, params, obs_rms, val_rms, obs, t, exp_obs, exp_act, exp_nlp, exp_val, exp_mu, exp_sigma,
                      exp_done, dones_prev, actions_out, seed, step, step_dev, eps_inject);
+  USV_CHECK_LAUNCH();
+  return 0;
+}
+
+int ppo_policy_bank_step(const ppo_cfg_t *cfg, const float *bank_params, const double *bank_obs_rms, const float *obs,
+                         int models, int group, float *actions_out, int grid_cap, void *stream) {
+  if (!cfg || !bank_params || !bank_obs_rms || !obs || !actions_out) return 1;
+  if (models < 1 || group < RB || group % RB != 0 || (long long)cfg->n_envs != (long long)models * group) return 2;
+  const int ntiles = cfg->n_envs / RB;
+  int grid = ntiles < 256 * POL_WPC ? ntiles : 256 * POL_WPC;
+  if (grid_cap > 0 && grid_cap < grid) grid = grid_cap;
+  hipLaunchKernelGGL(k_policy_bank, dim3(grid), dim3(TB), 0, (hipStream_t)stream, *cfg, bank_params, bank_obs_rms,
+                     obs, group, actions_out);
   USV_CHECK_LAUNCH();
   return 0;
 }

@@ -207,6 +207,16 @@
   X(USV_TEVS_CH_STRIDE, "USV_TEVS_CH_STRIDE") \
   X(USV_TEVS_RETURN, "USV_TEVS_RETURN") \
   X(USV_TEVS_N, "USV_TEVS_N") \
+  X(USV_BEV_SPEED_SUM, "USV_BEV_SPEED_SUM") \
+  X(USV_BEV_YAWRATE_SUM, "USV_BEV_YAWRATE_SUM") \
+  X(USV_BEV_ACT_SUM, "USV_BEV_ACT_SUM") \
+  X(USV_BEV_STEPS, "USV_BEV_STEPS") \
+  X(USV_BEV_ROWS, "USV_BEV_ROWS") \
+  X(USV_BEVS_SPEED_SUM, "USV_BEVS_SPEED_SUM") \
+  X(USV_BEVS_YAWRATE_SUM, "USV_BEVS_YAWRATE_SUM") \
+  X(USV_BEVS_ACT_SUM, "USV_BEVS_ACT_SUM") \
+  X(USV_BEVS_PAIRS, "USV_BEVS_PAIRS") \
+  X(USV_BEVS_N, "USV_BEVS_N") \
   X(USV_SCN_SITE_POSE, "USV_SCN_SITE_POSE") \
   X(USV_SCN_SITE_YAW, "USV_SCN_SITE_YAW") \
   X(USV_SCN_SITE_OBST, "USV_SCN_SITE_OBST") \
@@ -612,6 +622,11 @@
   X(offsetof(usv_teval_t, thr), "usv_teval.thr") \
   X(offsetof(usv_teval_t, level), "usv_teval.level") \
   X(offsetof(usv_teval_t, horizon), "usv_teval.horizon") \
+  X(sizeof(usv_bank_t), "sizeof usv_bank") \
+  X(offsetof(usv_bank_t, motion), "usv_bank.motion") \
+  X(offsetof(usv_bank_t, models), "usv_bank.models") \
+  X(offsetof(usv_bank_t, group), "usv_bank.group") \
+  X(offsetof(usv_bank_t, horizon), "usv_bank.horizon") \
   X(sizeof(ppo_cfg_t), "sizeof ppo_cfg") \
   X(offsetof(ppo_cfg_t, horizon), "ppo_cfg.horizon") \
   X(offsetof(ppo_cfg_t, n_envs), "ppo_cfg.n_envs") \
