@@ -1140,9 +1140,9 @@ int ppo_minibatch_coll_finish(const ppo_cfg_t *cfg, const ppo_adam_banks_t *bank
                               float grad_scale, float *kl_out, void *stream);
 
 /* size (floats) of the per-block partial-gradient scratch of ppo_minibatch_grad (16-byte aligned): one row per
- * 32-row workgroup, chunk-major ([128-slot chunk][workgroup][128]) for the reduction's contiguous reads, then the
- * group fold's rows and control words (after the larger of the two row layouts); <= 0 when minibatch is not a
- * positive multiple of 32 or the buffer would pass 2^31 floats -- the minibatch entry points return 2 then */
+ * 32-row workgroup, chunk-major ([128-slot chunk][workgroup][128]) for the reduction's contiguous reads, and
+ * nothing else; <= 0 when minibatch is not a positive multiple of 32 or the buffer would pass 2^31 - 1 floats --
+ * the minibatch entry points return 2 then */
 int ppo_partials_floats(int minibatch);
 /* size (floats) of the grad buffer of ppo_minibatch_grad / ppo_minibatch_apply */
 int ppo_grad_floats(void);

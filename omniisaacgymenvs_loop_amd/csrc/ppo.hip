@@ -1193,7 +1193,6 @@ struct ChainIn {
   float *kl_out;                           // minibatch k-1's KL (log)
   uint32_t *dp_clock;                      // several ranks: the minibatch counter the next reduction keys its
                                            // exchange on (advanced here, by workgroup 0; nullable)
-  int fold_skip;                           // group fold: arrive but fold nothing (tests: the reduction's raw-row path)
   float gscale;                            // collective chain (kColl): 1 / world, the all-reduced gradient's scale
 };
 
@@ -1214,7 +1213,6 @@ struct GradSmem {
   float b1[NH];
   float tail[TAIL + 1];
   float nrm[4];                   // chained update: wave sums of the chunk squares
-  int fold[2];                    // group fold: all members arrived, this launch's generation
 };
 
 // Partial-gradient slot layout (a permutation of the parameters, then the loss sums): the
@@ -1261,17 +1259,15 @@ struct RowIn {
 #ifndef USV_PART_AUX
 #define USV_PART_AUX 2   // cache-policy bits of the partial stores: nt (A/B builds override it)
 #endif
-// Partial layout.  Row-major (kCM false; the group fold's): row b = [NPART_PAD] at b NPART_PAD.  Chunk-major
-// (every other launch): the reduction's chunks of RD_P slots are the outer index, [chunk][nblk][RD_P],
+// Partial layout, chunk-major: the reduction's chunks of RD_P slots are the outer index, [chunk][nblk][RD_P],
 // so each reduction workgroup reads one contiguous nblk x RD_P block (128 KB at 8192 rows) instead of 256
 // segments 85 KB apart; a gradient workgroup writes its row as RED_BLOCKS segments of 512 B.
-template <int kAux, bool kCM>
+template <int kAux>
 struct PartOutT {
   __amdgpu_buffer_rsrc_t r;
-  uint32_t cs;   // chunk-major: bytes from one chunk of a row to the next (nblk RD_P 4)
+  uint32_t cs;   // bytes from one chunk of a row to the next (nblk RD_P 4)
   __device__ __forceinline__ uint32_t off(int idx) const {
-    if constexpr (kCM) return (uint32_t)(idx / RD_P) * cs + (uint32_t)(idx % RD_P) * 4u;
-    else return (uint32_t)idx * 4u;
+    return (uint32_t)(idx / RD_P) * cs + (uint32_t)(idx % RD_P) * 4u;
   }
   __device__ __forceinline__ void operator()(int idx, float v) const {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), r, off(idx), 0, kAux);
@@ -1282,43 +1278,6 @@ struct PartOutT {
     __builtin_amdgcn_raw_buffer_store_b128(v, r, off(idx), 0, kAux);   // idx % 4 == 0: inside one chunk
   }
 };
-constexpr int AUX_SC1 = 16;   // sc1: write-through (the in-launch group fold reads the rows from another CU)
-
-// ---- The XCD-group fold of the partial rows (kFold launches of k_mb_grad; k_reduce_partials(fold = 1)) ----
-// The 256 per-workgroup partial rows of an 8192-row minibatch (21.8 MB) were written by the gradient kernel and
-// read back whole by the reduction.  With the fold, workgroups b = g + 8 m (group g = b % 8, member m: the blocks
-// the dispatcher deals to one XCD, speed only -- correctness holds at any placement) meet at a per-group arrival
-// counter after storing their rows write-through (sc1, every wave drained); member m then sums the M = nblk / 8
-// rows of its group over slice m of the row (sc1 loads) and writes the group row's slice, so the reduction reads
-// 8 group rows per slot instead of nblk rows.  Summation order (the same bits in every path):
-//   group(g) = half0 + half1,  half0 = 0 + p[g] + p[g + 8] + ... (m < H0),  half1 = 0 + ... (H0 <= m < M),
-//   H0 = (M + 1) / 2;  gradient = 0 + group(0) + ... + group(7).
-// A member that does not see its whole group arrive within FOLD_WAIT_TICKS (another kernel or process holding
-// CUs: the group's rows cannot all be resident) folds nothing; the reduction then forms that group's sum from
-// the raw rows in the same order, so the result does not depend on whether a group folded.
-// Buffer (ppo_partials_floats): [nblk][NPART_PAD] rows | [8][NPART_PAD] group rows | fold control: per group
-// one 128-B line holding the arrival counter (monotonic: a member's arrival value tells its launch generation)
-// and 32 slice words (the generation whose fold wrote slice m).
-constexpr int FOLD_G = 8;
-static_assert(RD_G >= FOLD_G, "k_reduce_partials(fold = 1) reads one group row per row group");
-constexpr int FOLD_MAX_M = 32;                      // nblk <= 256: the grid is resident at one workgroup per CU
-constexpr int FOLD_CTL_STRIDE = 64;                 // u32 words per group: [0] counter, [32 + m] slice gens
-constexpr uint64_t FOLD_WAIT_TICKS = 10000;         // 100 us at the 100 MHz wall clock
-// floats in front of the fold control words: the larger of the chunk-major rows (RED_BLOCKS x RD_P per row, 112
-// floats more than a row-major row) and the row-major rows + the group rows, so every minibatch size has a layout
-__host__ __device__ constexpr size_t part_body_floats(int nblk) {
-  return (size_t)nblk * RED_BLOCKS * RD_P > (size_t)(nblk + FOLD_G) * NPART_PAD ? (size_t)nblk * RED_BLOCKS * RD_P
-                                                                                 : (size_t)(nblk + FOLD_G) * NPART_PAD;
-}
-__device__ __forceinline__ uint32_t *fold_ctl(float *partials, int nblk) {
-  return reinterpret_cast<uint32_t *>(partials + part_body_floats(nblk));
-}
-__device__ __forceinline__ const uint32_t *fold_ctl(const float *partials, int nblk) {
-  return reinterpret_cast<const uint32_t *>(partials + part_body_floats(nblk));
-}
-__device__ __forceinline__ f32x4v ld4_sc1(__amdgpu_buffer_rsrc_t r, uint32_t byte_off) {
-  return __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, AUX_SC1));
-}
 
 // One LDS-DMA wave-instruction: each active lane's 16 bytes at src go to LDS byte address lds_dst (wave-uniform)
 // + 16 lane, with no register in between.  Issued as inline assembly, so the compiler's wait counting does not
@@ -1396,7 +1355,7 @@ __device__ __forceinline__ float apply_norm_part(const float *__restrict__ grad_
 // kColl (several ranks without the peer exchange: ppo_minibatch_coll): ch.grad holds minibatch k-1's gradient and
 // KL after the host's in-stream SUM all-reduce; nothing was stepped speculatively, so every workgroup takes that
 // step itself (redo_step from bank prev with coefficient and scale, k_apply's norm of the scaled gradient).
-template <bool kBf, bool kChain, bool kFold, bool kColl = false>
+template <bool kBf, bool kChain, bool kColl = false>
 __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch, const float *__restrict__ P,
                                           const double *__restrict__ obs_rms, int row0,
                                           const float *__restrict__ e_obs, const float *__restrict__ e_act,
@@ -1418,7 +1377,7 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
   static_assert(NH * NH % GTB == 0, "staging trip counts");
   // kImg (the chained single-rank and peer-exchange launches): W2 comes from the image the previous
   // minibatch's reduction wrote behind ch.grad's chunk squares (W2IMG_OFF), by LDS-DMA; no w2f, no commit
-  constexpr bool kImg = kChain && !kColl && !kFold;
+  constexpr bool kImg = kChain && !kColl;
   float w2f[kImg ? 1 : NW2F];
   float w1r[NW1G], tlr[NTLG];
   // chained update: minibatch k-1's optimiser scalars (lanes 0-7) and KL (lane 8) as VECTOR loads,
@@ -1618,11 +1577,9 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
   }
   __syncthreads();
   USV_PHASE(ppo, 12);
-  constexpr bool kCM = !kFold;
-  const PartOutT<kFold ? AUX_SC1 : USV_PART_AUX, kCM> part_st{
-      kCM ? __builtin_amdgcn_make_buffer_rsrc(partials + (size_t)blockIdx.x * RD_P, 0,
-                                              (int)(((size_t)RED_BLOCKS * gridDim.x - blockIdx.x) * RD_P * 4), 0x00020000)
-          : __builtin_amdgcn_make_buffer_rsrc(partials + (size_t)blockIdx.x * NPART_PAD, 0, NPART * 4, 0x00020000),
+  const PartOutT<USV_PART_AUX> part_st{
+      __builtin_amdgcn_make_buffer_rsrc(partials + (size_t)blockIdx.x * RD_P, 0,
+                                        (int)(((size_t)RED_BLOCKS * gridDim.x - blockIdx.x) * RD_P * 4), 0x00020000),
       (uint32_t)gridDim.x * RD_P * 4u};
   // ---- heads: mu = Wmu h2 + bmu, value = Wv h2 + bv (16 threads per row, k = part + 16 kk: the 16
   // threads of a row read 16 consecutive words -- no 4-way LDS bank conflicts) ----
@@ -1882,70 +1839,9 @@ __device__ __forceinline__ void mb_grad8w(const ppo_cfg_t &c, const ChainIn &ch,
     }
   }
   USV_PHASE(ppo, 8);
-  if constexpr (kFold) {
-    // ---- the group fold (see FOLD_G): arrive once every wave's write-through stores are drained ----
-    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const int nblk = (int)gridDim.x, M = nblk / FOLD_G, g = blockIdx.x % FOLD_G, m = blockIdx.x / FOLD_G;
-    uint32_t *ctl = fold_ctl(partials, nblk) + g * FOLD_CTL_STRIDE;
-    if (tid == 0) {
-      // release: the members may sit on other XCDs (separate L2s); the memory model, not the write-through
-      // stores' drain alone, then orders this workgroup's row before its arrival
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      const uint32_t old = __hip_atomic_fetch_add(ctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const uint32_t gen = old / (uint32_t)M + 1u, target = gen * (uint32_t)M;
-      const uint64_t t0 = wall_clock64();
-      int ok = 0;
-      while (true) {
-        const uint32_t v = __hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sc1 poll
-        if ((int32_t)(v - target) >= 0) { ok = 1; __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); break; }
-        if (wall_clock64() - t0 > FOLD_WAIT_TICKS) break;
-        __builtin_amdgcn_s_sleep(1);
-      }
-      s.fold[0] = ok && !ch.fold_skip;
-      s.fold[1] = (int)gen;
-    }
-    __syncthreads();
-    USV_PHASE(ppo, 14);
-    if (s.fold[0]) {
-      constexpr int NQ = NPART_PAD / 4;
-      const int q4 = (NQ + M - 1) / M, qa = m * q4, qb = min(qa + q4, NQ);
-      const int h0 = (M + 1) / 2;
-      float4 *lds = reinterpret_cast<float4 *>(s.w2);   // the weights are no longer read
-      // the group's rows through one buffer descriptor (sc1 loads: served from L2 / memory, never L1)
-      const __amdgpu_buffer_rsrc_t rows = __builtin_amdgcn_make_buffer_rsrc(
-          partials + (size_t)g * NPART_PAD, 0, (int)((size_t)(nblk - g) * NPART_PAD * 4), 0x00020000);
-      float *grow = partials + (size_t)(nblk + g) * NPART_PAD;
-      for (int c0 = qa; c0 < qb; c0 += GTB / 2) {
-        const int half = tid / (GTB / 2), q = c0 + tid % (GTB / 2);
-        const int mb = half ? h0 : 0, me = half ? M : h0;
-        const int qc = min(q, NQ - 1);
-        f32x4v x[FOLD_MAX_M / 2];
-#pragma unroll
-        for (int k = 0; k < FOLD_MAX_M / 2; ++k)
-          x[k] = ld4_sc1(rows, (uint32_t)((FOLD_G * min(mb + k, M - 1) * NPART_PAD + 4 * qc) * 4));
-        f32x4v acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < FOLD_MAX_M / 2; ++k)
-          if (mb + k < me) acc += x[k];
-        if (half) lds[tid % (GTB / 2)] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        __syncthreads();
-        if (!half && q < qb) {
-          const float4 o = lds[tid];
-          const f32x4v t = {acc[0] + o.x, acc[1] + o.y, acc[2] + o.z, acc[3] + o.w};
-          __builtin_nontemporal_store(t, reinterpret_cast<f32x4v *>(grow + 4 * q));
-        }
-        __syncthreads();
-      }
-      __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) ctl[32 + m] = (uint32_t)s.fold[1];   // this slice of the group row is this launch's
-    }
-    USV_PHASE(ppo, 15);
-  }
 }
 
-template <bool kBf, bool kChain, bool kFold, bool kColl = false>
+template <bool kBf, bool kChain, bool kColl = false>
 __global__ __launch_bounds__(GTB, 2) void k_mb_grad(ppo_cfg_t c, ChainIn ch, const float *__restrict__ P,
                                                     const double *__restrict__ obs_rms, int row0,
                                                     const float *__restrict__ e_obs, const float *__restrict__ e_act,
@@ -1953,11 +1849,11 @@ __global__ __launch_bounds__(GTB, 2) void k_mb_grad(ppo_cfg_t c, ChainIn ch, con
                                                     const float *__restrict__ e_ret, const float *__restrict__ e_adv,
                                                     float *e_mu, float *e_sigma, float *partials) {
   __shared__ GradSmem s;
-  mb_grad8w<kBf, kChain, kFold, kColl>(c, ch, P, obs_rms, row0, e_obs, e_act, e_nlp, e_val, e_ret, e_adv, e_mu,
-                                       e_sigma, partials, s);
+  mb_grad8w<kBf, kChain, kColl>(c, ch, P, obs_rms, row0, e_obs, e_act, e_nlp, e_val, e_ret, e_adv, e_mu, e_sigma,
+                                partials, s);
 }
 
-// k_reduce_partials: the per-workgroup partial rows (stride NPART_PAD floats, 16-B aligned)
+// k_reduce_partials: the per-workgroup partial rows (chunk-major, PartOutT)
 // summed in a fixed order (deterministic, independent of the launch) into grad[].
 // One 512-thread workgroup per 128 consecutive slots (param_of_slot maps them back to the
 // parameter order of grad[]): each half-wave loads a 512-B
@@ -2107,7 +2003,7 @@ __global__ __launch_bounds__(RD_TB) void k_dp_selftest(ppo_dp_t dp, uint32_t key
 template <bool kSpec, bool kDP>
 __global__ __launch_bounds__(RD_TB) void k_reduce_partials(const float *__restrict__ partials, int nblk, float *grad,
                                                            float *losses, float inv_b, ppo_cfg_t c, AdamBanks a,
-                                                           const float *__restrict__ opt_in, ppo_dp_t dp, int fold) {
+                                                           const float *__restrict__ opt_in, ppo_dp_t dp) {
   __shared__ float4 red[RD_G][RD_L];
   __shared__ float sqw[RD_TB / 64];
   USV_PHASE(red, 0);
@@ -2132,28 +2028,6 @@ __global__ __launch_bounds__(RD_TB) void k_reduce_partials(const float *__restri
 #pragma unroll
     for (int q = 0; q < 8; ++q) oin[q] = opt_in[q];
   }
-  const int p4c = min(p4, NPART_PAD / 4 - 1);
-  if (fold) {   // the gradient kernel folded the rows of group g = grp (FOLD_G): one group row per group
-    if (grp < FOLD_G) {
-      const int M = nblk / FOLD_G;
-      const uint32_t *ctl = fold_ctl(partials, nblk) + grp * FOLD_CTL_STRIDE;
-      const uint32_t gen = ctl[0] / (uint32_t)M;
-      bool folded = true;
-      for (int mm = 0; mm < M; ++mm) folded &= ctl[32 + mm] == gen;
-      if (folded) {
-        acc = P4[(size_t)(nblk + grp) * (NPART_PAD / 4) + p4c];
-      } else {   // a member timed out: the same sums from the raw rows, in the fold's order
-        const int h0 = (M + 1) / 2;
-        float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-        for (int mm = 0; mm < M; ++mm) {
-          const float4 x = P4[(size_t)(grp + FOLD_G * mm) * (NPART_PAD / 4) + p4c];
-          float4 &t = mm < h0 ? a0 : a1;
-          t.x += x.x; t.y += x.y; t.z += x.z; t.w += x.w;
-        }
-        acc = make_float4(a0.x + a1.x, a0.y + a1.y, a0.z + a1.z, a0.w + a1.w);
-      }
-    }
-  } else
   for (int b0 = grp; b0 < nblk; b0 += RD_G * RD_KB) {
     // branch-free: clamped rows / columns loaded, masked in the sum (every load in flight at once)
     float4 x[RD_KB];
@@ -2421,55 +2295,6 @@ int ppo_prepare(const ppo_cfg_t *cfg, const float *params, const double *obs_rms
   return 0;
 }
 
-// the XCD-group fold of the partial rows (FOLD_G): minibatches of 8 x 1..32 workgroups (the whole grid resident at
-// one workgroup per CU).  Off by default: same-box A/B at 131072 envs (profiles/r04/r04c_fold_ab.txt), rocprof
-// means fold 22.57 + 5.11 us vs 18.39 + 7.00 us without (write-through partial stores and the group wait
-// +1.5 us, the fold's own load / store round 3.6 us, against 1.9 us saved in the reduction, whose time is its
-// fixed latency rather than the 21.8 MB it reads).  USV_PPO_FOLD=1 turns it on; USV_PPO_FOLD=2: every member
-// arrives but none folds -- the reduction's raw-row path, for the tests.
-static int fold_env() {
-  const char *e = getenv("USV_PPO_FOLD");
-  return e ? atoi(e) : 0;
-}
-static bool fold_on(int nblk) {
-  return fold_env() != 0 && nblk % FOLD_G == 0 && nblk / FOLD_G >= 1 && nblk / FOLD_G <= FOLD_MAX_M;
-}
-
-int ppo_minibatch_grad(const ppo_cfg_t *cfg, const float *params, double *obs_rms, const double *val_rms,
-                       int update_obs_rms, int mb_index, const float *exp_obs, const float *exp_act,
-                       const float *exp_nlp, const float *exp_val, const float *exp_ret, const float *exp_adv,
-                       float *exp_mu, float *exp_sigma, float *grad, float *losses, float *partials, double *work,
-                       void *stream) {
-  (void)val_rms;
-  if (!cfg || !params || !obs_rms || !grad || !partials || !work) return 1;
-  if (cfg->minibatch % RB != 0 || ppo_partials_floats(cfg->minibatch) <= 0) return 2;   // no partial layout
-  if (reinterpret_cast<uintptr_t>(params) & 15u) return 4;   // 16-byte weight staging loads
-  hipStream_t s = (hipStream_t)stream;
-  const int row0 = mb_index * cfg->minibatch;
-  if (update_obs_rms && cfg->normalize_input) {
-    // RunningMeanStd.train on the minibatch obs (mini-epoch 0 only, a2c_common.py:1243-1244);
-    // partials at work[8..], completion counter in the bits of work[7]
-    const int nb = 64;
-    hipLaunchKernelGGL(k_obs_stats, dim3(nb), dim3(TB), 0, s, *cfg, exp_obs, row0, cfg->minibatch, work + 8, obs_rms,
-                       reinterpret_cast<unsigned *>(work + 7));
-    USV_CHECK_LAUNCH();
-  }
-  if (reinterpret_cast<uintptr_t>(partials) & 15u) return 3;
-  const int nblk = cfg->minibatch / RB;
-  const bool fold = fold_on(nblk);
-  ChainIn ch{};
-  ch.fold_skip = fold_env() == 2;
-  hipLaunchKernelGGL((cfg->bf16_gemm ? (fold ? k_mb_grad<true, false, true> : k_mb_grad<true, false, false>)
-                                     : (fold ? k_mb_grad<false, false, true> : k_mb_grad<false, false, false>)),
-                     dim3(nblk), dim3(GTB), 0, s, *cfg, ch, params, obs_rms, row0, exp_obs, exp_act, exp_nlp,
-                     exp_val, exp_ret, exp_adv, exp_mu, exp_sigma, partials);
-  USV_CHECK_LAUNCH();
-  hipLaunchKernelGGL((k_reduce_partials<false, false>), dim3(RED_BLOCKS), dim3(RD_TB), 0, s, partials, nblk, grad,
-                     losses, 1.0f / (float)cfg->minibatch, *cfg, AdamBanks{}, nullptr, ppo_dp_t{}, (int)fold);
-  USV_CHECK_LAUNCH();
-  return 0;
-}
-
 static bool banks_ok(const ppo_adam_banks_t *b) {
   if (!b || !b->opt) return false;
   for (int i = 0; i < 2; ++i) {
@@ -2479,16 +2304,89 @@ static bool banks_ok(const ppo_adam_banks_t *b) {
   return true;
 }
 
+// ---- the launch sequence behind ppo_minibatch_grad, fused_launch and ppo_minibatch_coll: the shared argument
+// checks, k_obs_stats, the gradient kernel, the reduction ----
+struct ExpRows {   // the experience buffers a minibatch reads (mu / sigma: written back)
+  const float *obs, *act, *nlp, *val, *ret, *adv;
+  float *mu, *sigma;
+};
+// 2: no partial layout; 3: partials (and, where the caller passes it, grad: the chained gradient kernel copies
+// the W2 image behind the chunk squares in 16-byte pieces) not 16-byte aligned
+static int mb_check(const ppo_cfg_t *cfg, const float *partials, const float *grad16) {
+  if (cfg->minibatch % RB != 0 || ppo_partials_floats(cfg->minibatch) <= 0) return 2;
+  if ((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(grad16)) & 15u) return 3;
+  return 0;
+}
+// RunningMeanStd.train on the minibatch obs (mini-epoch 0 only, a2c_common.py:1243-1244);
+// partials at work[8..], completion counter in the bits of work[7]
+static int launch_obs_stats(const ppo_cfg_t *cfg, int update_obs_rms, const float *exp_obs, int row0, double *obs_rms,
+                            double *work, hipStream_t s) {
+  if (!update_obs_rms || !cfg->normalize_input) return 0;
+  hipLaunchKernelGGL(k_obs_stats, dim3(64), dim3(TB), 0, s, *cfg, exp_obs, row0, cfg->minibatch, work + 8, obs_rms,
+                     reinterpret_cast<unsigned *>(work + 7));
+  USV_CHECK_LAUNCH();
+  return 0;
+}
+// the one place that names k_mb_grad's instantiations: {bf16, fp32} x {plain, chained, collective chain}
+static int launch_mb_grad(const ppo_cfg_t *cfg, bool chain, bool coll, const ChainIn &ch, const float *P,
+                          const double *obs_rms, int row0, const ExpRows &e, float *partials, hipStream_t s) {
+  const bool bf = cfg->bf16_gemm != 0;
+  auto *k = bf ? k_mb_grad<true, false> : k_mb_grad<false, false>;
+  if (chain) k = bf ? k_mb_grad<true, true> : k_mb_grad<false, true>;
+  if (chain && coll) k = bf ? k_mb_grad<true, true, true> : k_mb_grad<false, true, true>;
+  hipLaunchKernelGGL(k, dim3(cfg->minibatch / RB), dim3(GTB), 0, s, *cfg, ch, P, obs_rms, row0, e.obs, e.act, e.nlp,
+                     e.val, e.ret, e.adv, e.mu, e.sigma, partials);
+  USV_CHECK_LAUNCH();
+  return 0;
+}
+// spec: the reduction also takes the speculative Adam step a.*0 -> a.*1 on the scalars opt_in (the chained
+// update); dp (with spec only): the chunk is exchanged between the ranks before that step
+static int launch_reduce(const ppo_cfg_t *cfg, const float *partials, float *grad, float *losses, bool spec,
+                         const AdamBanks &a, const float *opt_in, const ppo_dp_t *dp, hipStream_t s) {
+  auto *k = k_reduce_partials<false, false>;
+  if (spec) k = dp ? k_reduce_partials<true, true> : k_reduce_partials<true, false>;
+  hipLaunchKernelGGL(k, dim3(RED_BLOCKS), dim3(RD_TB), 0, s, partials, cfg->minibatch / RB, grad, losses,
+                     1.0f / (float)cfg->minibatch, *cfg, a, opt_in, dp ? *dp : ppo_dp_t{});
+  USV_CHECK_LAUNCH();
+  return 0;
+}
+// minibatch seq's chain inputs: none for seq 0, else minibatch seq - 1's step from bank (seq - 1) % 2 into seq % 2
+static ChainIn chain_in(const ppo_adam_banks_t *b, int seq, const float *grad, float *kl_prev_out) {
+  ChainIn ch{};
+  if (seq == 0) return ch;
+  const int cur = seq & 1, prv = cur ^ 1;
+  ch.P_prev = b->params[prv]; ch.m_prev = b->m[prv]; ch.v_prev = b->v[prv];
+  ch.P_cur = b->params[cur]; ch.m_cur = b->m[cur]; ch.v_cur = b->v[cur];
+  ch.grad = grad;
+  ch.opt_prev = b->opt + 8 * prv;
+  ch.opt_cur = b->opt + 8 * cur;
+  ch.kl_out = kl_prev_out;
+  return ch;
+}
+
+int ppo_minibatch_grad(const ppo_cfg_t *cfg, const float *params, double *obs_rms, const double *val_rms,
+                       int update_obs_rms, int mb_index, const float *exp_obs, const float *exp_act,
+                       const float *exp_nlp, const float *exp_val, const float *exp_ret, const float *exp_adv,
+                       float *exp_mu, float *exp_sigma, float *grad, float *losses, float *partials, double *work,
+                       void *stream) {
+  (void)val_rms;
+  if (!cfg || !params || !obs_rms || !grad || !partials || !work) return 1;
+  if (int rc = mb_check(cfg, partials, nullptr)) return rc;
+  if (reinterpret_cast<uintptr_t>(params) & 15u) return 4;   // 16-byte weight staging loads
+  hipStream_t s = (hipStream_t)stream;
+  const int row0 = mb_index * cfg->minibatch;
+  const ExpRows e{exp_obs, exp_act, exp_nlp, exp_val, exp_ret, exp_adv, exp_mu, exp_sigma};
+  if (int rc = launch_obs_stats(cfg, update_obs_rms, exp_obs, row0, obs_rms, work, s)) return rc;
+  if (int rc = launch_mb_grad(cfg, false, false, ChainIn{}, params, obs_rms, row0, e, partials, s)) return rc;
+  return launch_reduce(cfg, partials, grad, losses, false, AdamBanks{}, nullptr, nullptr, s);
+}
+
 static int fused_launch(const ppo_cfg_t *cfg, const ppo_adam_banks_t *banks, const ppo_dp_t *dp, int seq,
-                        double *obs_rms, int update_obs_rms, int mb_index, const float *exp_obs, const float *exp_act,
-                        const float *exp_nlp, const float *exp_val, const float *exp_ret, const float *exp_adv,
-                        float *exp_mu, float *exp_sigma, float *grad, float *losses, float *partials, double *work,
-                        float *kl_prev_out, void *stream) {
+                        double *obs_rms, int update_obs_rms, int mb_index, const ExpRows &e, float *grad,
+                        float *losses, float *partials, double *work, float *kl_prev_out, void *stream) {
   if (!cfg || !obs_rms || !grad || !partials || !work || seq < 0) return 1;
   if (!banks_ok(banks)) return 4;
-  if (cfg->minibatch % RB != 0 || ppo_partials_floats(cfg->minibatch) <= 0) return 2;   // no partial layout
-  // (grad: the chained gradient kernel copies the W2 image behind the chunk squares in 16-byte pieces)
-  if ((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(grad)) & 15u) return 3;
+  if (int rc = mb_check(cfg, partials, grad)) return rc;
   if (dp) {
     if (dp->world < 1 || dp->world > PPO_DP_MAX || dp->rank < 0 || dp->rank >= dp->world || !dp->clock || !dp->err)
       return 5;
@@ -2496,44 +2394,14 @@ static int fused_launch(const ppo_cfg_t *cfg, const ppo_adam_banks_t *banks, con
       if (!dp->peer[r]) return 5;
   }
   hipStream_t s = (hipStream_t)stream;
-  const int cur = seq & 1, prv = cur ^ 1, nblk = cfg->minibatch / RB, row0 = mb_index * cfg->minibatch;
-  if (update_obs_rms && cfg->normalize_input) {
-    hipLaunchKernelGGL(k_obs_stats, dim3(64), dim3(TB), 0, s, *cfg, exp_obs, row0, cfg->minibatch, work + 8, obs_rms,
-                       reinterpret_cast<unsigned *>(work + 7));
-    USV_CHECK_LAUNCH();
-  }
-  const float *P = banks->params[cur];
-  const dim3 gg(nblk), gb(GTB);
-  uint32_t *clk = dp ? dp->clock : nullptr;
-  const bool fold = fold_on(nblk);
-  if (seq == 0) {
-    ChainIn ch{};
-    ch.dp_clock = clk;
-    ch.fold_skip = fold_env() == 2;
-    hipLaunchKernelGGL((cfg->bf16_gemm ? (fold ? k_mb_grad<true, false, true> : k_mb_grad<true, false, false>)
-                                       : (fold ? k_mb_grad<false, false, true> : k_mb_grad<false, false, false>)),
-                       gg, gb, 0, s, *cfg, ch, P, obs_rms, row0, exp_obs, exp_act, exp_nlp, exp_val, exp_ret, exp_adv,
-                       exp_mu, exp_sigma, partials);
-  } else {
-    const ChainIn ch{banks->params[prv], banks->m[prv], banks->v[prv], banks->params[cur], banks->m[cur],
-                     banks->v[cur], grad, banks->opt + 8 * prv, banks->opt + 8 * cur, kl_prev_out, clk,
-                     fold_env() == 2};
-    hipLaunchKernelGGL((cfg->bf16_gemm ? (fold ? k_mb_grad<true, true, true> : k_mb_grad<true, true, false>)
-                                       : (fold ? k_mb_grad<false, true, true> : k_mb_grad<false, true, false>)),
-                       gg, gb, 0, s, *cfg, ch, P, obs_rms, row0, exp_obs, exp_act, exp_nlp, exp_val, exp_ret, exp_adv,
-                       exp_mu, exp_sigma, partials);
-  }
-  USV_CHECK_LAUNCH();
+  const int cur = seq & 1, prv = cur ^ 1, row0 = mb_index * cfg->minibatch;
+  ChainIn ch = chain_in(banks, seq, grad, kl_prev_out);
+  ch.dp_clock = dp ? dp->clock : nullptr;
   const AdamBanks a{banks->params[cur], banks->m[cur], banks->v[cur], banks->params[prv], banks->m[prv],
                     banks->v[prv]};
-  if (dp)
-    hipLaunchKernelGGL((k_reduce_partials<true, true>), dim3(RED_BLOCKS), dim3(RD_TB), 0, s, partials, nblk, grad,
-                       losses, 1.0f / (float)cfg->minibatch, *cfg, a, banks->opt + 8 * cur, *dp, (int)fold);
-  else
-    hipLaunchKernelGGL((k_reduce_partials<true, false>), dim3(RED_BLOCKS), dim3(RD_TB), 0, s, partials, nblk, grad,
-                       losses, 1.0f / (float)cfg->minibatch, *cfg, a, banks->opt + 8 * cur, ppo_dp_t{}, (int)fold);
-  USV_CHECK_LAUNCH();
-  return 0;
+  if (int rc = launch_obs_stats(cfg, update_obs_rms, e.obs, row0, obs_rms, work, s)) return rc;
+  if (int rc = launch_mb_grad(cfg, seq > 0, false, ch, banks->params[cur], obs_rms, row0, e, partials, s)) return rc;
+  return launch_reduce(cfg, partials, grad, losses, true, a, banks->opt + 8 * cur, dp, s);
 }
 
 int ppo_minibatch_fused(const ppo_cfg_t *cfg, const ppo_adam_banks_t *banks, int seq, double *obs_rms,
@@ -2541,8 +2409,9 @@ int ppo_minibatch_fused(const ppo_cfg_t *cfg, const ppo_adam_banks_t *banks, int
                         const float *exp_nlp, const float *exp_val, const float *exp_ret, const float *exp_adv,
                         float *exp_mu, float *exp_sigma, float *grad, float *losses, float *partials, double *work,
                         float *kl_prev_out, void *stream) {
-  return fused_launch(cfg, banks, nullptr, seq, obs_rms, update_obs_rms, mb_index, exp_obs, exp_act, exp_nlp, exp_val,
-                      exp_ret, exp_adv, exp_mu, exp_sigma, grad, losses, partials, work, kl_prev_out, stream);
+  const ExpRows e{exp_obs, exp_act, exp_nlp, exp_val, exp_ret, exp_adv, exp_mu, exp_sigma};
+  return fused_launch(cfg, banks, nullptr, seq, obs_rms, update_obs_rms, mb_index, e, grad, losses, partials, work,
+                      kl_prev_out, stream);
 }
 
 int ppo_minibatch_fused_dp(const ppo_cfg_t *cfg, const ppo_adam_banks_t *banks, const ppo_dp_t *dp, int seq,
@@ -2551,8 +2420,9 @@ int ppo_minibatch_fused_dp(const ppo_cfg_t *cfg, const ppo_adam_banks_t *banks, 
                            const float *exp_adv, float *exp_mu, float *exp_sigma, float *grad, float *losses,
                            float *partials, double *work, float *kl_prev_out, void *stream) {
   if (!dp) return 5;
-  return fused_launch(cfg, banks, dp, seq, obs_rms, update_obs_rms, mb_index, exp_obs, exp_act, exp_nlp, exp_val,
-                      exp_ret, exp_adv, exp_mu, exp_sigma, grad, losses, partials, work, kl_prev_out, stream);
+  const ExpRows e{exp_obs, exp_act, exp_nlp, exp_val, exp_ret, exp_adv, exp_mu, exp_sigma};
+  return fused_launch(cfg, banks, dp, seq, obs_rms, update_obs_rms, mb_index, e, grad, losses, partials, work,
+                      kl_prev_out, stream);
 }
 
 // Several ranks without the peer exchange (the RCCL fallback): two launches per minibatch and an in-stream SUM
@@ -2568,34 +2438,15 @@ int ppo_minibatch_coll(const ppo_cfg_t *cfg, const ppo_adam_banks_t *banks, int 
                        float *kl_prev_out, void *stream) {
   if (!cfg || !obs_rms || !grad || !partials || !work || seq < 0 || !(grad_scale > 0.f)) return 1;
   if (!banks_ok(banks)) return 4;
-  if (cfg->minibatch % RB != 0 || ppo_partials_floats(cfg->minibatch) <= 0) return 2;   // no partial layout
-  if ((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(grad)) & 15u) return 3;
+  if (int rc = mb_check(cfg, partials, grad)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int cur = seq & 1, prv = cur ^ 1, nblk = cfg->minibatch / RB, row0 = mb_index * cfg->minibatch;
-  if (update_obs_rms && cfg->normalize_input) {
-    hipLaunchKernelGGL(k_obs_stats, dim3(64), dim3(TB), 0, s, *cfg, exp_obs, row0, cfg->minibatch, work + 8, obs_rms,
-                       reinterpret_cast<unsigned *>(work + 7));
-    USV_CHECK_LAUNCH();
-  }
-  const float *P = banks->params[cur];
-  if (seq == 0) {
-    ChainIn ch{};
-    hipLaunchKernelGGL((cfg->bf16_gemm ? k_mb_grad<true, false, false> : k_mb_grad<false, false, false>), dim3(nblk),
-                       dim3(GTB), 0, s, *cfg, ch, P, obs_rms, row0, exp_obs, exp_act, exp_nlp, exp_val, exp_ret,
-                       exp_adv, exp_mu, exp_sigma, partials);
-  } else {
-    const ChainIn ch{banks->params[prv], banks->m[prv], banks->v[prv], banks->params[cur], banks->m[cur],
-                     banks->v[cur], grad, banks->opt + 8 * prv, banks->opt + 8 * cur, kl_prev_out, nullptr, 0,
-                     grad_scale};
-    hipLaunchKernelGGL((cfg->bf16_gemm ? k_mb_grad<true, true, false, true> : k_mb_grad<false, true, false, true>),
-                       dim3(nblk), dim3(GTB), 0, s, *cfg, ch, P, obs_rms, row0, exp_obs, exp_act, exp_nlp, exp_val,
-                       exp_ret, exp_adv, exp_mu, exp_sigma, partials);
-  }
-  USV_CHECK_LAUNCH();
-  hipLaunchKernelGGL((k_reduce_partials<false, false>), dim3(RED_BLOCKS), dim3(RD_TB), 0, s, partials, nblk, grad,
-                     losses, 1.0f / (float)cfg->minibatch, *cfg, AdamBanks{}, nullptr, ppo_dp_t{}, 0);
-  USV_CHECK_LAUNCH();
-  return 0;
+  const int row0 = mb_index * cfg->minibatch;
+  const ExpRows e{exp_obs, exp_act, exp_nlp, exp_val, exp_ret, exp_adv, exp_mu, exp_sigma};
+  ChainIn ch = chain_in(banks, seq, grad, kl_prev_out);
+  ch.gscale = grad_scale;
+  if (int rc = launch_obs_stats(cfg, update_obs_rms, exp_obs, row0, obs_rms, work, s)) return rc;
+  if (int rc = launch_mb_grad(cfg, seq > 0, true, ch, banks->params[seq & 1], obs_rms, row0, e, partials, s)) return rc;
+  return launch_reduce(cfg, partials, grad, losses, false, AdamBanks{}, nullptr, nullptr, s);
 }
 
 int ppo_minibatch_coll_finish(const ppo_cfg_t *cfg, const ppo_adam_banks_t *banks, int count, const float *grad,
@@ -2701,11 +2552,11 @@ int ppo_minibatch_apply(const ppo_cfg_t *cfg, float *params, float *grad, float 
   return 0;
 }
 
-// per-workgroup rows, the fold's group rows and its control lines (zero-initialised by the caller)
+// the chunk-major per-workgroup rows (PartOutT): scratch, nothing to initialise
 int ppo_partials_floats(int minibatch) {
   static_assert(RED_BLOCKS * RD_P >= NPART_PAD, "chunk-major rows cover a partial row");
   if (minibatch < RB || minibatch % RB != 0) return -1;
-  const long long f = (long long)part_body_floats(minibatch / RB) + FOLD_G * FOLD_CTL_STRIDE;
+  const long long f = (long long)(minibatch / RB) * RED_BLOCKS * RD_P;
   return f > 0x7fffffffLL ? -1 : (int)f;
 }
 // gradient + loss sums, chunk squares, the W2 image (16-byte aligned in a 16-byte aligned buffer)

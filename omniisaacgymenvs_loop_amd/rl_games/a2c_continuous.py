@@ -341,28 +341,36 @@ class A2CAgent:
         obs = self.vec_env.reset()
         return obs
 
+    def _policy_step(self, n: int, step: int, s: int) -> None:
+        """ppo_policy_step of rollout slot n (Philox step `step`) on the current observations and dones, stream s."""
+        c = _capi
+        obs = self._obs_in(self.obs["obs"]["state"] if isinstance(self.obs["obs"], dict) else self.obs["obs"])
+        c.call("ppo_policy_step", c.byref(self.cfg), c.ptr(self.model_params), c.ptr(self.obs_rms),
+               c.ptr(self.val_rms), c.ptr(obs), n, c.ptr(self.exp_obs), c.ptr(self.exp_act), c.ptr(self.exp_nlp),
+               c.ptr(self.exp_val), c.ptr(self.exp_mu), c.ptr(self.exp_sigma), c.ptr(self.exp_done),
+               c.ptr(self.dones), c.ptr(self.actions), self.seed + 7919 * self.rank, step, c.ptr(self.step_dev),
+               None, s)
+
+    def _store_reward(self, n: int, rewards: torch.Tensor, dones: torch.Tensor, s: int) -> None:
+        """ppo_store_reward of rollout slot n on stream s."""
+        c = _capi
+        c.call("ppo_store_reward", c.byref(self.cfg), c.ptr(rewards), c.ptr(dones), n, c.ptr(self.exp_rew),
+               c.ptr(self.cur_rew), c.ptr(self.cur_shaped), c.ptr(self.cur_len), c.ptr(self.meter_buf),
+               c.ptr(self.step_dev), s)
+
     def play_steps(self) -> Dict[str, Any]:
         """A2CBase.play_steps (a2c_common.py:670-774): H x (policy kernel, env kernels, reward kernel)."""
         if os.getenv("USV_STEP_OVERLAP", "1") != "0" and hasattr(self.vec_env, "step_async"):
             return self._play_steps_overlapped()
-        c = _capi
-        cfg = c.byref(self.cfg)
-        s = c.stream_ptr()
+        s = _capi.stream_ptr()
         self.meter.zero_()
         step_time = 0.0
         for n in range(self.horizon_length):
-            obs = self._obs_in(self.obs["obs"]["state"] if isinstance(self.obs["obs"], dict) else self.obs["obs"])
-            c.call("ppo_policy_step", cfg, c.ptr(self.model_params), c.ptr(self.obs_rms), c.ptr(self.val_rms),
-                   c.ptr(obs), n, c.ptr(self.exp_obs), c.ptr(self.exp_act), c.ptr(self.exp_nlp),
-                   c.ptr(self.exp_val), c.ptr(self.exp_mu), c.ptr(self.exp_sigma), c.ptr(self.exp_done),
-                   c.ptr(self.dones), c.ptr(self.actions), self.seed + 7919 * self.rank, self._step_counter,
-                   c.ptr(self.step_dev), None, s)
+            self._policy_step(n, self._step_counter, s)
             t0 = time.time()
             self.obs, rewards, self.dones, infos = self.vec_env.step(self.actions)
             step_time += time.time() - t0
-            c.call("ppo_store_reward", cfg, c.ptr(rewards), c.ptr(self.dones), n, c.ptr(self.exp_rew),
-                   c.ptr(self.cur_rew), c.ptr(self.cur_shaped), c.ptr(self.cur_len), c.ptr(self.meter_buf),
-                   c.ptr(self.step_dev), s)
+            self._store_reward(n, rewards, self.dones, s)
             self.algo_observer.process_infos(infos, None)
             self._step_counter += 1
         return {"played_frames": self.batch_size, "step_time": step_time}
@@ -373,25 +381,10 @@ class A2CAgent:
         final on this stream while the reset envs' potential fields and deferred rewards finish on a side
         stream; store_reward(n) waits for them (vec_env.join()).  Every kernel sees the inputs it sees in
         the sequential loop, so the experience buffers, meters and env state are the same bits."""
-        c = _capi
-        cfg = c.byref(self.cfg)
-        s = c.stream_ptr()
+        s = _capi.stream_ptr()
         self.meter.zero_()
         step_time = 0.0
         base = self._step_counter
-
-        def policy(n):
-            obs = self._obs_in(self.obs["obs"]["state"] if isinstance(self.obs["obs"], dict) else self.obs["obs"])
-            c.call("ppo_policy_step", cfg, c.ptr(self.model_params), c.ptr(self.obs_rms), c.ptr(self.val_rms),
-                   c.ptr(obs), n, c.ptr(self.exp_obs), c.ptr(self.exp_act), c.ptr(self.exp_nlp),
-                   c.ptr(self.exp_val), c.ptr(self.exp_mu), c.ptr(self.exp_sigma), c.ptr(self.exp_done),
-                   c.ptr(self.dones), c.ptr(self.actions), self.seed + 7919 * self.rank, base + n,
-                   c.ptr(self.step_dev), None, s)
-
-        def store(n, rewards, dones):
-            c.call("ppo_store_reward", cfg, c.ptr(rewards), c.ptr(dones), n, c.ptr(self.exp_rew),
-                   c.ptr(self.cur_rew), c.ptr(self.cur_shaped), c.ptr(self.cur_len), c.ptr(self.meter_buf),
-                   c.ptr(self.step_dev), s)
 
         # USV_STORE_DEFER=1 (default): store_reward(n) runs inside step n + 1 once its fields have forked (the
         # env kernels that overwrite step n's rewards / dones follow it), so it leaves the field chain -- the
@@ -399,21 +392,21 @@ class A2CAgent:
         # store follows its join.  0: right after each join
         defer = os.getenv("USV_STORE_DEFER", "1") == "1"
         pending = None
-        policy(0)
+        self._policy_step(0, base, s)
         for n in range(self.horizon_length):
             t0 = time.time()
-            hook = (lambda p=pending: store(*p)) if pending is not None else None
+            hook = (lambda p=pending: self._store_reward(*p, s)) if pending is not None else None
             self.obs, rewards, self.dones, infos = self.vec_env.step_async(self.actions, chain=n > 0,
                                                                            after_fork=hook)
             step_time += time.time() - t0
             if n + 1 < self.horizon_length:
-                policy(n + 1)
+                self._policy_step(n + 1, base + n + 1, s)
             self.vec_env.join()
             if defer and n + 1 < self.horizon_length:
                 pending = (n, rewards, self.dones)
             else:
                 pending = None
-                store(n, rewards, self.dones)
+                self._store_reward(n, rewards, self.dones, s)
             self.algo_observer.process_infos(infos, None)
         self._step_counter = base + self.horizon_length
         return {"played_frames": self.batch_size, "step_time": step_time}
@@ -456,6 +449,17 @@ class A2CAgent:
         return (self._dp_ranks and getattr(self, "_dp", None) is None and os.environ.get("USV_PPO_FUSED", "1") != "0"
                 and os.environ.get("USV_DP_COLL_CHAIN", "1") != "0")
 
+    def _mb_args(self, seq: bool, mini_ep: int, i: int, k: int) -> tuple:
+        """The arguments every minibatch entry point shares, obs_rms to work, for minibatch i of mini-epoch mini_ep
+        (position k in the update): with the epoch's RunningMeanStd sequence (seq) mini-epoch 0 normalises with
+        the statistics after merge i and no call updates them."""
+        c = _capi
+        rms = self.rms_seq[2 * NIN * i:] if seq and mini_ep == 0 else self.obs_rms
+        return (c.ptr(rms), int(mini_ep == 0 and not seq), i, c.ptr(self.exp_obs), c.ptr(self.exp_act),
+                c.ptr(self.exp_nlp), c.ptr(self.exp_val), c.ptr(self.exp_ret), c.ptr(self.exp_adv), c.ptr(self.exp_mu),
+                c.ptr(self.exp_sigma), c.ptr(self.grad), c.ptr(self.loss_log[k]), c.ptr(self.partials),
+                c.ptr(self.work))
+
     def update_epoch_minibatches(self) -> None:
         """The mini-epoch / minibatch loop (a2c_common.py:1190-1245): per minibatch the gradient kernel
         (+ fixed-order partial reduction), [RCCL all-reduce of the flat gradient + KL with several
@@ -476,11 +480,7 @@ class A2CAgent:
             fn = "ppo_minibatch_fused_dp" if dpx else "ppo_minibatch_fused"
             for mini_ep in range(self.mini_epochs_num):
                 for i in range(self.num_minibatches):
-                    rms = self.rms_seq[2 * NIN * i:] if seq and mini_ep == 0 else self.obs_rms
-                    c.call(fn, cfg, banks, *dpx, k, c.ptr(rms), int(mini_ep == 0 and not seq), i,
-                           c.ptr(self.exp_obs), c.ptr(self.exp_act), c.ptr(self.exp_nlp), c.ptr(self.exp_val),
-                           c.ptr(self.exp_ret), c.ptr(self.exp_adv), c.ptr(self.exp_mu), c.ptr(self.exp_sigma),
-                           c.ptr(self.grad), c.ptr(self.loss_log[k]), c.ptr(self.partials), c.ptr(self.work),
+                    c.call(fn, cfg, banks, *dpx, k, *self._mb_args(seq, mini_ep, i, k),
                            c.ptr(self.kls[k - 1:k]) if k else None, s)
                     k += 1
             c.call("ppo_minibatch_finish", cfg, banks, k, c.ptr(self.grad), c.ptr(self.kls[k - 1:k]), s)
@@ -493,12 +493,8 @@ class A2CAgent:
             scale = 1.0 / dist_util.world()
             for mini_ep in range(self.mini_epochs_num):
                 for i in range(self.num_minibatches):
-                    rms = self.rms_seq[2 * NIN * i:] if seq and mini_ep == 0 else self.obs_rms
-                    c.call("ppo_minibatch_coll", cfg, banks, k, float(scale), c.ptr(rms),
-                           int(mini_ep == 0 and not seq), i, c.ptr(self.exp_obs), c.ptr(self.exp_act),
-                           c.ptr(self.exp_nlp), c.ptr(self.exp_val), c.ptr(self.exp_ret), c.ptr(self.exp_adv),
-                           c.ptr(self.exp_mu), c.ptr(self.exp_sigma), c.ptr(self.grad), c.ptr(self.loss_log[k]),
-                           c.ptr(self.partials), c.ptr(self.work), c.ptr(self.kls[k - 1:k]) if k else None, s)
+                    c.call("ppo_minibatch_coll", cfg, banks, k, float(scale), *self._mb_args(seq, mini_ep, i, k),
+                           c.ptr(self.kls[k - 1:k]) if k else None, s)
                     self._allreduce_grad()
                     k += 1
             c.call("ppo_minibatch_coll_finish", cfg, banks, k, c.ptr(self.grad), float(scale),
@@ -507,12 +503,8 @@ class A2CAgent:
             return
         for mini_ep in range(self.mini_epochs_num):
             for i in range(self.num_minibatches):
-                rms = self.rms_seq[2 * NIN * i:] if seq and mini_ep == 0 else self.obs_rms
-                args = (cfg, c.ptr(self.model_params), c.ptr(rms), c.ptr(self.val_rms), int(mini_ep == 0 and not seq), i,
-                        c.ptr(self.exp_obs), c.ptr(self.exp_act), c.ptr(self.exp_nlp), c.ptr(self.exp_val),
-                        c.ptr(self.exp_ret), c.ptr(self.exp_adv), c.ptr(self.exp_mu), c.ptr(self.exp_sigma),
-                        c.ptr(self.grad), c.ptr(self.loss_log[k]), c.ptr(self.partials), c.ptr(self.work))
-                c.call("ppo_minibatch_grad", *args, s)
+                rms, *rest = self._mb_args(seq, mini_ep, i, k)
+                c.call("ppo_minibatch_grad", cfg, c.ptr(self.model_params), rms, c.ptr(self.val_rms), *rest, s)
                 scale = self._allreduce_grad()
                 c.call("ppo_minibatch_apply", cfg, c.ptr(self.model_params), c.ptr(self.grad),
                        c.ptr(self.adam_m), c.ptr(self.adam_v), c.ptr(self.opt), k % 2, float(scale),

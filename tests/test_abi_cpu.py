@@ -114,9 +114,9 @@ def test_stale_root_needs_its_rows():
 
 def test_partials_layout_for_every_minibatch_and_refused_sizes():
     """ppo_partials_floats covers any positive multiple of 32 rows (the reference yaml's horizon x num_envs minibatch,
-    e.g. 65,536 or loopz-sized 76,800 rows, included): the fold control words follow the larger of the chunk-major
-    rows (RED_BLOCKS x 128 floats per 32-row block) and the row-major rows + group rows.  Sizes without a layout
-    are refused by the minibatch entry points with status 2 before any device work (argument checks only)."""
+    e.g. 65,536 or loopz-sized 76,800 rows, included) and is exactly the chunk-major rows (RED_BLOCKS x 128 floats
+    per 32-row block).  Sizes without a layout are refused by the minibatch entry points with status 2 before any
+    device work (argument checks only)."""
     from omniisaacgymenvs_loop_amd import _capi
     from omniisaacgymenvs_loop_amd._abi import DEFINES, PpoCfg
     if not os.path.exists(_capi.LIB_PATH):
@@ -126,7 +126,7 @@ def test_partials_layout_for_every_minibatch_and_refused_sizes():
     prev = 0
     for mb in (32, 8192, 48576, 48608, 65536, 76800, 262144):
         f = lib.ppo_partials_floats(mb)
-        assert f >= (mb // 32) * red_blocks * 128 + 8 * 64 and f > prev, (mb, f)
+        assert f == (mb // 32) * red_blocks * 128 and f > prev, (mb, f)
         prev = f
     for mb in (0, 16, 8200, 2 ** 31 - 32):
         assert lib.ppo_partials_floats(mb) <= 0, mb

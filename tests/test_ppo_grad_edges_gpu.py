@@ -43,12 +43,12 @@ class Rig:
             setattr(ag.cfg, k, v)
         self.gf, self.pf = c.lib().ppo_grad_floats(), c.lib().ppo_partials_floats(rows)
         assert self.gf == ag.grad.numel() and self.pf == ag.partials.numel()
-        # floats the nblk partial rows take: the size's slope in the row-block count where the chunk-major rows
-        # set it (from ~1,500 workgroups on; below, the fold's row-major layout with its 8 group rows is larger)
+        # floats the nblk partial rows take: the size's slope in the row-block count (the chunk-major rows are the
+        # whole buffer)
         lib = c.lib()
         row = (lib.ppo_partials_floats(32 * 8192) - lib.ppo_partials_floats(32 * 4096)) // 4096
         self.used = rows // 32 * row
-        assert PO.NPARAM + 8 <= row < PO.NPARAM + 8 + 128 and self.used <= self.pf
+        assert PO.NPARAM + 8 <= row < PO.NPARAM + 8 + 128 and self.used == self.pf
         self.grad = torch.full((self.gf + PAD,), SENT, device=DEV)
         self.partials = torch.full((self.pf + PAD,), SENT, device=DEV)
         self.grad[:self.gf] = 0
@@ -83,7 +83,7 @@ class Rig:
         # nothing is written behind the sizes the library states
         assert bool((self.grad[self.gf:].view(torch.int32) == _bits(SENT)).all()), "grad tail written"
         assert bool((self.partials[self.pf:].view(torch.int32) == _bits(SENT)).all()), "partials tail written"
-        # ... nor, without the group fold, behind the nblk rows (the fold's group rows and control words stay zero)
+        # ... nor behind the nblk rows (used == pf: the rows end where the buffer does)
         assert bool((self.partials[self.used:self.pf].view(torch.int32) == 0).all()), "partials past nblk rows written"
         return out
 
@@ -205,7 +205,7 @@ def test_row_offset_takes_the_second_minibatch():
     np.testing.assert_array_equal(out["sigma"][96:], out0["sigma"])
 
 
-@pytest.mark.parametrize("rows", [96, 8224])
+@pytest.mark.parametrize("rows", [96, 544, 8224])
 def test_repeat_is_bit_identical(rows):
     case = R.make_case("stress", rows)
     rig = Rig(rows)
@@ -214,21 +214,6 @@ def test_repeat_is_bit_identical(rows):
     rig.restore()
     b = rig.run()
     _bitwise_equal(a, b)
-
-
-@pytest.mark.parametrize("rows", [544, 8224])
-def test_fold_declines_when_groups_are_uneven(rows, monkeypatch):
-    """USV_PPO_FOLD=1 with nblk % 8 != 0 (17, 257 workgroups): the XCD-group fold has no layout and must decline,
-    leaving the unfolded path's bits."""
-    case = R.make_case("boundary", rows)
-    rig = Rig(rows)
-    rig.load(case)
-    outs = []
-    for mode in ("0", "1"):
-        monkeypatch.setenv("USV_PPO_FOLD", mode)
-        rig.restore()
-        outs.append(rig.run())
-    _bitwise_equal(*outs)
 
 
 # ---------------------------------------------------------------- observation statistics under the gradient
